@@ -26,6 +26,12 @@ process group must hold exactly N ranks.
 a HIP graph after the warm-up / autotune steps and times its replays: at 32x32 a layer is
 a few microseconds of GPU work, less than the host's launch cost.
 
+A plain run sets up, warms up, times exactly --steps steps and prints the headline.  --full adds
+what takes runs of its own: the roofline records of the dominant kernels, the CPU baselines and
+the config-2 / 3 / 5 lines (config2_cifar32, config3_mobilenet32, config5_mobilevit256).
+--dump-outputs DIR writes the logits of the last timed step to DIR/logits.npy (float32); inputs
+and weights are seeded, so two builds run with the same arguments compare output for output.
+
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
 """
 import argparse
@@ -289,6 +295,27 @@ def gather_buffer(rows, classes, dev):
     return torch.empty(dist.get_world_size() * rows, classes, device=dev)
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every tensor of `arrays` as path/<name>.npy, float32 (float64 stays float64), at
+    most DUMP_MAX_BYTES over all of them: a larger tensor is cut to a fixed sample of its flattened
+    elements (indices drawn once from a seeded generator, sorted), the same from run to run."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(len(arrays), 1) - 256  # per file, less the .npy header
+    for name, t in arrays.items():
+        t = t.detach()
+        a = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+        if a.nbytes > budget:
+            keep = budget // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def leg_steps(replay, floor, seconds, probe=20):
     """Timed steps of a graph-replayed config leg: at least `floor`, and enough for `seconds` of GPU work
     (estimated from `probe` untimed replays), so an outside sampler of GPU activity sees the leg."""
@@ -302,23 +329,28 @@ def leg_steps(replay, floor, seconds, probe=20):
     return max(int(floor), int(math.ceil(seconds / max(per, 1e-6))))
 
 
-def timed_steps(step, steps, warmup, world, sync, dev):
+def timed_steps(step, steps, warmup, world, sync, dev, record=True, last=None):
     """`warmup` untimed steps, then exactly `steps` timed ones bracketed by a barrier +
-    device sync on both sides; returns the MAX wall time over ranks (seconds)."""
+    device sync on both sides; returns the MAX wall time over ranks (seconds).  `record` is
+    handed to the timed steps (HIP events around the dominant op); a list given as `last`
+    receives what the last timed step returned."""
     for _ in range(warmup):
         step()
     sync()
     if world > 1:
         dist.barrier()
     sync()
+    out = None
     t0 = time.perf_counter()
     for _ in range(steps):
-        step(record=True)
+        out = step(record=record)
     sync()
     if world > 1:
         dist.barrier()
     sync()
     dt = time.perf_counter() - t0
+    if last is not None:
+        last.append(out)
     if world > 1:
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -721,9 +753,18 @@ def main():
                     help="process-group backend for N > 1 (nccl = RCCL over xGMI on ROCm)")
     ap.add_argument("--selftest", action="store_true",
                     help="N-rank plumbing only (gloo, CPU stand-in logits, no kernels): launcher, gather, timing")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the rooflines of the dominant kernels, the CPU baselines "
+                         "and the config-2/3/5 lines (--no-cpu-baseline / --no-cifar / --no-models drop one each); "
+                         "a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the logits, gathered over the ranks) to "
+                         "DIR/logits.npy as float32")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU: start the N ranks (nothing has touched the GPU in this process)
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -796,18 +837,65 @@ def main():
                 logits = chain.forward(x)
         gstep = lambda record=False: gather_logits(graph.replay() or logits, gathered, world)  # noqa: E731
 
+    last = []
     with torch.no_grad():
-        # autotuning needs one untimed pass
+        # autotuning needs one untimed pass; the dominant op's events are recorded for --full's roofline only
         dt = timed_steps(gstep if graph is not None else step, args.steps,
-                         max(args.warmup, 1 if _lib.benchmark else 0), world, torch.cuda.synchronize, dev)
+                         max(args.warmup, 1 if _lib.benchmark else 0), world, torch.cuda.synchronize, dev,
+                         record=args.full, last=last)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": last[0]})
 
-    # dominant op (HIP events on its stream): the stage-1 conv pair (conv1 -> conv2 of a block
-    # in one launch) when the chain runs pairs, else the fused quantize+conv of the timed shape
     pair_used = chain.pairable(0, x)
     pair32_used = chain.pair and args.quantizer in ("po2", "po2+") and \
         _lib.pair_supported((B, 32, Hs // 2, Hs // 2), args.bits, args.quantizer)
     s2ds_used = chain.s2ds and args.quantizer in ("po2", "po2+") and \
         _lib.s2ds_supported((B, 16, Hs, Hs), args.bits, args.quantizer)
+    _, C, K, R, st, pad, _ = chain.layers[chain.timed_layer]
+    # the conv arithmetic the library actually planned for this layer (AUTO picks
+    # bf16x3 for power-of-two weights): three exact bf16 MFMA passes per fp32 product
+    plan = _lib.describe(B, C, Hs, Hs, K, R, R, st, pad, 1, 1, args.bits,
+                         None if args.quantizer == "none" else args.quantizer, 1, args.precision)
+    prec = "bf16x3" if "kind=bf16x3" in plan else "fp32"
+    images = world * B * args.steps
+    out = {
+        "metric": METRIC, "value": round(images / dt, 2), "unit": "images/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3 / args.steps, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "fp32" if prec == "fp32" else "fp32(bf16x3)", "data": "synthetic",
+        "config": {"workload": "%s quantized-conv chain: %d fused %s-%dbit quantize+conv fwd + head%s%s%s%s"
+                               % (args.model, len(chain.layers), args.quantizer, args.bits,
+                                  (" (stage-1%s conv1->conv2 pairs as one launch each)"
+                                   % (" and stage-2" if pair32_used else "")) if pair_used else "",
+                                  " (stride-2 conv1 + 1x1 shortcut of stages 2-3 as one launch each)"
+                                  if s2ds_used else "",
+                                  " (weight packs of the single-conv layers batched: one launch per 36)"
+                                  if chain.packed is not None else "",
+                                  " + RCCL all_gather(logits)" if world > 1 else ""),
+                   "conv_pairs": pair_used,
+                   "conv_pairs_stage2": pair32_used,
+                   "s2ds": s2ds_used,
+                   "pack_batch": chain.packed is not None,
+                   "autotune": _lib.benchmark,
+                   "image": Hs, "batch_per_gpu": B, "global_batch": world * B, "quantizer": args.quantizer,
+                   "bits": args.bits, "precision": prec, "parallelism": "dp%d" % world, "world_size": world,
+                   "dist_backend": backend, "hip_graph": graph is not None},
+        "full": args.full,
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:  # a plain run ends with the headline
+        finish()
+        return
+
+    # --full.  Dominant op (HIP events on its stream): the stage-1 conv pair (conv1 -> conv2 of a block
+    # in one launch) when the chain runs pairs, else the fused quantize+conv of the timed shape
     xl = torch.relu(torch.randn(args.batch, 16, args.image, args.image, device=dev))
 
     def launch_avg_ms(fn, reps=20):
@@ -842,13 +930,7 @@ def main():
     else:
         ev_ms = [a.elapsed_time(b) for a, b in chain.events]
         avg_ms = sum(ev_ms) / max(len(ev_ms), 1)
-    _, C, K, R, st, pad, _ = chain.layers[chain.timed_layer]
     flops, nbytes = conv_work(B, C, Hs, K, R, st, pad)
-    # the conv arithmetic the library actually planned for this layer (AUTO picks
-    # bf16x3 for power-of-two weights): three exact bf16 MFMA passes per fp32 product
-    plan = _lib.describe(B, C, Hs, Hs, K, R, R, st, pad, 1, 1, args.bits,
-                         None if args.quantizer == "none" else args.quantizer, 1, args.precision)
-    prec = "bf16x3" if "kind=bf16x3" in plan else "fp32"
     peak_c = PEAK_BF16_MFMA_TFLOPS / 3.0 if prec == "bf16x3" else PEAK_FP32_MFMA_TFLOPS
 
     def roofline(fl, nb, ms):
@@ -894,33 +976,7 @@ def main():
                      "flops": int(flops)})
         layer_roof = None
 
-    images = world * B * args.steps
-    out = {
-        "metric": METRIC, "value": round(images / dt, 2), "unit": "images/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3 / args.steps, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "fp32" if prec == "fp32" else "fp32(bf16x3)", "data": "synthetic",
-        "config": {"workload": "%s quantized-conv chain: %d fused %s-%dbit quantize+conv fwd + head%s%s%s%s"
-                               % (args.model, len(chain.layers), args.quantizer, args.bits,
-                                  (" (stage-1%s conv1->conv2 pairs as one launch each)"
-                                   % (" and stage-2" if pair32_used else "")) if pair_used else "",
-                                  " (stride-2 conv1 + 1x1 shortcut of stages 2-3 as one launch each)"
-                                  if s2ds_used else "",
-                                  " (weight packs of the single-conv layers batched: one launch per 36)"
-                                  if chain.packed is not None else "",
-                                  " + RCCL all_gather(logits)" if world > 1 else ""),
-                   "conv_pairs": pair_used,
-                   "conv_pairs_stage2": pair32_used,
-                   "s2ds": s2ds_used,
-                   "pack_batch": chain.packed is not None,
-                   "autotune": _lib.benchmark,
-                   "image": Hs, "batch_per_gpu": B, "global_batch": world * B, "quantizer": args.quantizer,
-                   "bits": args.bits, "precision": prec, "parallelism": "dp%d" % world, "world_size": world,
-                   "dist_backend": backend, "hip_graph": graph is not None},
-        "roofline": roof,
-        "layer_roofline": layer_roof,
-        "cpu_baseline": None,
-    }
+    out.update({"roofline": roof, "layer_roofline": layer_roof, "cpu_baseline": None})
     # the CPU baselines run on rank 0 at N = 1 only: at N > 1 the other ranks would poll the next
     # barrier beside it and skew the number
     cpu_leg = rank == 0 and world == 1 and not args.no_cpu_baseline
@@ -938,11 +994,7 @@ def main():
         torch.cuda.empty_cache()
         out["config5_mobilevit256"] = model_extra(args, world, rank, dev, "mobilevit", "po2+", 2, 256, 64, 1000, 50,
                                                   cpu_leg, "MobileViT-XS (config 5)")
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

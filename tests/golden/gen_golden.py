@@ -16,6 +16,8 @@ Writes (all data, no reference source):
                   inputs + outputs, bits 2/3/4, default and explicit num_iters
   models.json     state_dict key/shape lists of the reference models (checkpoint
                   compatibility of the drop-in modules)
+quant_kat, conv_kat and lin_kat are written as <name>.partNN.npz of under 1 MiB each
+(parts.py; tests/_util.load_npz reads them back as one mapping).
 """
 import json
 import os
@@ -28,6 +30,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REF = "/root/reference"
 sys.path.insert(0, HERE)
 from fill import seeded_fill_  # noqa: E402
+from parts import save_parts  # noqa: E402  (the larger files are stored as <name>.partNN.npz)
 
 
 def f32(bits):
@@ -91,7 +94,7 @@ def gen_quant(thr):
             out["apply/%s/%s/4" % (name, mode)] = y
             y = q.forward(None, torch.from_numpy(x.copy()), 4, 2).numpy()
             out["fsr2/%s/%s/4" % (name, mode)] = y
-    np.savez_compressed(os.path.join(HERE, "quant_kat.npz"), **out)
+    save_parts(os.path.join(HERE, "quant_kat.npz"), out)
     print("quant_kat.npz:", len(out), "arrays")
 
 
@@ -148,7 +151,7 @@ def gen_conv():
         out["y64/" + name] = y64.numpy()
         meta.append(dict(name=name, N=N, C=C, H=H, W=W, K=K, R=R, S=S, stride=st, pad=pad,
                          dil=dil, groups=grp, bias=bias, mode=mode, bits=bits))
-    np.savez_compressed(os.path.join(HERE, "conv_kat.npz"), **out)
+    save_parts(os.path.join(HERE, "conv_kat.npz"), out)
     with open(os.path.join(HERE, "conv_kat.json"), "w") as f:
         json.dump(meta, f, indent=1)
     print("conv_kat.npz:", len(meta), "cases")
@@ -185,7 +188,7 @@ def gen_lin():
             out["apply/%s/%s/4" % (name, qn)] = q.apply(torch.from_numpy(x.copy()), 4).numpy()
             for it in (0, 3):
                 out["it%d/%s/%s/4" % (it, name, qn)] = q.forward(None, torch.from_numpy(x.copy()), 4, it).numpy()
-    np.savez_compressed(os.path.join(HERE, "lin_kat.npz"), **out)
+    save_parts(os.path.join(HERE, "lin_kat.npz"), out)
     print("lin_kat.npz:", len(out), "arrays")
 
 

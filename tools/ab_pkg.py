@@ -52,9 +52,11 @@ def run_arm(root, what, extra=None):
     if what == "pair":
         cmd = [sys.executable, "-c", PAIR]
     elif what == "cifar":  # the config-2 chain (ResNet56 @32, HIP graph) of bench.py's extra line
-        cmd = [sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-models"]
+        cmd = [sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+               "--no-models"]
     elif what == "models":  # the config-3 / config-5 lines (MobileNetV2 @32, MobileViT-XS @256, HIP graphs)
-        cmd = [sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-cifar"]
+        cmd = [sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+               "--no-cifar"]
     else:
         cmd = [sys.executable, "bench.py", "--steps", "30", "--warmup", "3", "--no-cpu-baseline", "--no-cifar",
                "--no-models"]

@@ -36,8 +36,8 @@ for s in $STEPS; do
                if ! grep -q " passed" gpurun_out/convtests.log || grep -q "failed\|error" gpurun_out/convtests.log; then
                    echo "stopping: conv GPU tests did not pass"; exit 1
                fi ;;
-        bench) run bench 600 python bench.py ;;
-        benchnp) run benchnp 600 python bench.py --steps 5 --warmup 2 --no-pair --no-cpu-baseline ;;
+        bench) run bench 600 python bench.py --full ;;
+        benchnp) run benchnp 600 python bench.py --full --steps 5 --warmup 2 --no-pair --no-cpu-baseline ;;
         models) run models_c2 300 python tools/model_bench.py --model resnet56 --image 32 --classes 10 --graph
                 run models_c3 300 python tools/model_bench.py --model mobilenet --image 32 --classes 10 --quantizer po2+ --graph
                 run models_c5 300 python tools/model_bench.py --model mobilevit --image 256 --batch 64 --quantizer po2+ --bits 2 --graph
@@ -92,8 +92,8 @@ for s in $STEPS; do
              run qatb 600 python tools/qat_bench.py resnet56 ;;
         layers) run layers 600 python tools/layer_bench.py --torch ;;
         layers32) run layers32 600 python tools/layer_bench.py --image 32 --tune --torch ;;
-        bench32) run bench32 600 python bench.py --image 32 --steps 20 --warmup 3 --no-cpu-baseline ;;
-        bench32g) run bench32g 600 python bench.py --image 32 --steps 50 --warmup 3 --graph --no-cpu-baseline ;;
+        bench32) run bench32 600 python bench.py --full --image 32 --steps 20 --warmup 3 --no-cpu-baseline ;;
+        bench32g) run bench32g 600 python bench.py --full --image 32 --steps 50 --warmup 3 --graph --no-cpu-baseline ;;
         sweep) run sweep 900 python tools/tile_sweep.py ;;
         profc2) run profc2 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/profc2 -o run \
                   -- python bench.py --image 32 --steps 50 --warmup 3 --graph --no-cpu-baseline --no-cifar --no-models ;;
