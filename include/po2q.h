@@ -23,12 +23,36 @@ extern "C" {
 #endif
 
 /* quantizer selection — the reference's quantizer_dict keys (utils/quantizers.py:156-161)
- * plus "no quantizer" (QuantizedConv2d with quantize_fn=None, quantized_conv.py:37-38) */
-enum po2q_mode { PO2Q_MODE_NONE = 0, PO2Q_MODE_PO2 = 1, PO2Q_MODE_PO2_PLUS = 2 };
+ * plus "no quantizer" (QuantizedConv2d with quantize_fn=None, quantized_conv.py:37-38).
+ *
+ * PO2Q_MODE_LIN / PO2Q_MODE_LIN_PLUS (LinearPowerOfTwoQuantizer / ...PlusQuantizer) are conv modes
+ * only: the single-conv entries (po2q_qconv2d_* below and the plan handles, po2q_qconv2d_plan_pack_batch
+ * included) take them; the quantizer entries po2q_quantize_f32 / _f64 / _bf16 keep rejecting them
+ * (lin has po2q_quantize_lin_f32) and the multi-layer entries (pair, s2ds, chain, ir) return 0 from
+ * their *_supported queries and PO2Q_ERR_UNSUPPORTED from their run entries.
+ * In the lin modes the `fsr` argument of every entry carries num_iters (>= 0): the reference puts
+ * the two in the same positional slot, forward(ctx, input, bits, fsr) against
+ * forward(ctx, input, bits, num_iters).
+ * Precision of the lin modes: after one refit the step delta_c is a power of two and Q(w) =
+ * delta_c * q with an integer |q| <= 2^(bits-1) - 1, so for groups == 1, 1 <= bits <= 9 and
+ * num_iters >= 1 Q(w) is exact in bf16 and PO2Q_PREC_AUTO takes the bf16x3 kernels (scale 1).
+ * Otherwise (grouped / depthwise layers, bits 10..16, num_iters == 0) AUTO takes the fp32 kernels on
+ * the lin-quantized weight, and PO2Q_PREC_BF16X3 returns PO2Q_ERR_UNSUPPORTED.
+ * Range limit: the bf16x3 result is exact while every nonzero |Q(w)| is a normal bf16, i.e. every
+ * delta_c >= 2^-126; below that the matrix unit may flush the weight to zero.
+ * A NaN Q(w) (a constant channel, or a NaN / inf in the channel) is packed as a bf16 NaN. */
+enum po2q_mode {
+    PO2Q_MODE_NONE = 0,
+    PO2Q_MODE_PO2 = 1,
+    PO2Q_MODE_PO2_PLUS = 2,
+    PO2Q_MODE_LIN = 3,
+    PO2Q_MODE_LIN_PLUS = 4
+};
 
 /* conv arithmetic (flags of po2q_qconv2d_f32) */
 enum po2q_precision {
-    PO2Q_PREC_AUTO = 0,   /* BF16X3 when eligible (po2/po2+ weights, groups == 1), else FP32 */
+    PO2Q_PREC_AUTO = 0,   /* BF16X3 when eligible (po2/po2+ weights, groups == 1; lin/lin+: see po2q_mode),
+                             else FP32 */
     PO2Q_PREC_FP32 = 1,   /* fp32-input MFMA, exact fp32 fma chain (any weights) */
     PO2Q_PREC_BF16X3 = 2  /* bf16 MFMA on exact operands: weights Q(w)/scale = +-2^e, activations
                              split by truncation into hi+mid+lo bf16 (exact); fp32 accumulation.

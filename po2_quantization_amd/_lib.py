@@ -23,7 +23,9 @@ _DEFAULT_LIB = os.path.join(_HERE, "lib", "libpo2q.so")
 LIB_PATH = os.environ.get("PO2Q_LIB", _DEFAULT_LIB)
 OPS_PATH = os.path.join(_HERE, "lib", "libpo2q_torch.so")
 
-MODES = {None: 0, "none": 0, "po2": 1, "po2+": 2}
+# "lin" / "lin+" are conv modes only (qconv2d*, pack_batch, plans, describe); the `fsr` argument of
+# those calls carries num_iters for them (include/po2q.h, enum po2q_mode)
+MODES = {None: 0, "none": 0, "po2": 1, "po2+": 2, "lin": 3, "lin+": 4}
 PRECISIONS = {"auto": 0, "fp32": 1, "bf16x3": 2}
 # fused epilogue activations (include/po2q.h enum po2q_act)
 ACTS = {None: 0, "none": 0, "relu": 1, "relu6": 2, "silu": 3}
@@ -157,6 +159,10 @@ def load():
     L.po2q_qconv2d_pair_supported.argtypes = [i64] * 4 + [i32] * 3
     L.po2q_qconv2d_s2ds_supported.restype = i32
     L.po2q_qconv2d_s2ds_supported.argtypes = [i64] * 4 + [i32] * 3
+    L.po2q_qconv2d_pair_f32.restype = i32
+    L.po2q_qconv2d_pair_f32.argtypes = [p] * 4 + [i64] * 4 + [i32] * 3 + [p] * 4 + [i32] + [p] * 3 + [i32, p]
+    L.po2q_qconv2d_s2ds_f32.restype = i32
+    L.po2q_qconv2d_s2ds_f32.argtypes = [p] * 5 + [i64] * 4 + [i32] * 3 + [p, p, i32, p, p, p]
     L.po2q_qconv2d_plan_create.restype = i32
     L.po2q_qconv2d_plan_create.argtypes = [ctypes.POINTER(p), i32] + [i64] * 14 + [i32] * 4
     L.po2q_qconv2d_plan_workspace_bytes.restype = sz
@@ -237,7 +243,7 @@ def quantize(w, bits, mode, fsr=1):
     if not isinstance(w, torch.Tensor):
         raise TypeError("po2q: input must be a torch.Tensor")
     mode_id = MODES[mode]
-    if mode_id == 0:
+    if mode_id not in (1, 2):
         raise Po2qError("po2q: quantize() needs mode 'po2' or 'po2+'")
     native = w.device.type == "cuda" and w.dtype in (torch.float32, torch.float64, torch.bfloat16)
     if not native:
@@ -643,9 +649,12 @@ def qconv2d_packed(x, w, workspace, bias=None, stride=1, padding=0, dilation=1, 
                     post_scale, post_shift, residual, ACTS[act])
 
 
-def ir_shape_supported(x_shape, Ch, Cout, stride, expand):
+def ir_shape_supported(x_shape, Ch, Cout, stride, expand, mode="po2"):
     """Whether the fused inverted-residual kernel takes this block by default (po2q_qconv2d_ir_shape_supported:
-    where it measured faster than the three layer launches).  Host-only."""
+    where it measured faster than the three layer launches).  Host-only.  Never for the lin modes:
+    the C entry takes no mode, po2q_qconv2d_ir_supported rejects lin plans."""
+    if mode not in ("po2", "po2+"):
+        return False
     N, Cin, H, W = (int(v) for v in x_shape)
     return load().po2q_qconv2d_ir_shape_supported(N, Cin, H, W, int(Ch), int(Cout), int(stride), int(bool(expand))) == 1
 

@@ -26,8 +26,11 @@ namespace {
 constexpr size_t kAlign = 256;
 size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
 
+// allow_none: the conv entries, which also take the lin modes (the quantizer entries take neither:
+// lin has po2q_quantize_lin_f32)
 bool check_mode_bits(int mode, int bits, bool allow_none) {
-    if (mode != PO2Q_MODE_PO2 && mode != PO2Q_MODE_PO2_PLUS && !(allow_none && mode == PO2Q_MODE_NONE)) {
+    if (mode != PO2Q_MODE_PO2 && mode != PO2Q_MODE_PO2_PLUS &&
+        !(allow_none && (mode == PO2Q_MODE_NONE || is_lin_mode(mode)))) {
         set_error("po2q: unknown quantizer mode " + std::to_string(mode));
         return false;
     }
@@ -140,9 +143,9 @@ int po2q_quantize_lin_f32(const float* w, float* out, int64_t d0, int64_t d1, in
                       "lin quantize launch");
 }
 
-// Workspace layout: [absmax partials][scale (bf16x3)][packed weights]
+// Workspace layout: [absmax partials][scale (bf16x3)][packed weights][lin / lin+: delta[Cg]]
 struct WsLayout {
-    size_t part_bytes, scale_off, packed_off, total;
+    size_t part_bytes, scale_off, packed_off, delta_off, total;
     int nparts;  // 0: absmax fused into the bf16x3 pack kernel
 };
 
@@ -151,11 +154,12 @@ static WsLayout ws_layout(const ConvPlan& p, int mode) {
     const int64_t nw = (int64_t)p.K * p.Cg * p.R * p.S;
     const bool fused = (is_bf16x3_kind(p.kind) || p.kind == KIND_DEPTHWISE) &&
                        nw <= kFusedAbsmaxMax;
-    L.nparts = (mode == PO2Q_MODE_NONE || fused) ? 0 : absmax_blocks(nw);
+    L.nparts = (mode == PO2Q_MODE_NONE || is_lin_mode(mode) || fused) ? 0 : absmax_blocks(nw);
     L.part_bytes = align_up((size_t)absmax_blocks(nw) * sizeof(unsigned));
     L.scale_off = L.part_bytes;
     L.packed_off = L.scale_off + kAlign;
-    L.total = L.packed_off + align_up((size_t)p.packed_floats * sizeof(float));
+    L.delta_off = L.packed_off + align_up((size_t)p.packed_floats * sizeof(float));
+    L.total = L.delta_off + (is_lin_mode(mode) ? align_up((size_t)p.Cg * sizeof(float)) : 0);
     return L;
 }
 
@@ -178,9 +182,17 @@ size_t po2q_qconv2d_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, 
     return total;
 }
 
+static bool check_lin_iters(int mode, int fsr) {
+    if (is_lin_mode(mode) && fsr < 0) {
+        set_error("po2q: lin / lin+ need num_iters >= 0 (passed as fsr), got " + std::to_string(fsr));
+        return false;
+    }
+    return true;
+}
+
 static int check_conv_args(const float* x, const float* w, float* y, void* workspace, int mode, int bits,
-                           int flags) {
-    if (!check_mode_bits(mode, bits, true)) return PO2Q_ERR_INVALID;
+                           int flags, int fsr) {
+    if (!check_mode_bits(mode, bits, true) || !check_lin_iters(mode, fsr)) return PO2Q_ERR_INVALID;
     if (flags < PO2Q_PREC_AUTO || flags > PO2Q_PREC_BF16X3) {
         set_error("po2q: unknown precision flag " + std::to_string(flags));
         return PO2Q_ERR_INVALID;
@@ -206,8 +218,14 @@ static bool plan_packs_weight(const ConvPlan& p, int /*mode*/) {
     return true;
 }
 
+// Phase 1 job of a lin plan: the weight [K, Cg, R, S] has Cg dim-1 channels of K * R * S elements.
+static LinReq lin_req(const ConvPlan& p, const float* w, float* delta, int bits, int num_iters, int mode) {
+    return LinReq{w, delta, p.K, p.Cg, p.R * p.S, bits, num_iters, mode == PO2Q_MODE_LIN_PLUS ? 1 : 0};
+}
+
 // phases of run_plan: the weight quantize + pack into the workspace, the conv from it
-enum { RUN_PACK = 1, RUN_CONV = 2, RUN_ALL = 3 };
+// (RUN_PACK2: a lin plan's pack alone, its steps already in the workspace -- the batched pack)
+enum { RUN_PACK = 1, RUN_CONV = 2, RUN_ALL = 3, RUN_PACK2 = 4 };
 
 // Enqueue the fused quantize(+pack) and conv of plan p on stream s (+ the epilogue e:
 // in the row kernels' store epilogue where they support it, else one elementwise pass).
@@ -224,7 +242,17 @@ static int run_plan(const ConvPlan& p, const float* x, const float* w, const flo
     float* scale = reinterpret_cast<float*>(ws + L.scale_off);
     void* packed = ws + L.packed_off;
     const int64_t nw = (int64_t)p.K * p.Cg * p.R * p.S;
+    float* delta = is_lin_mode(mode) ? reinterpret_cast<float*>(ws + L.delta_off) : nullptr;
     int st;
+    if (is_lin_mode(mode) && (p.fp || p.kind == KIND_DIRECT_F32 || p.kind == KIND_PW_F32)) {
+        set_error("po2q: lin / lin+ have no plan with in-kernel weight staging or an unpacked weight");
+        return PO2Q_ERR_INVALID;
+    }
+    if (delta && (phases & RUN_PACK)) {  // phase 1: the per-channel steps (fsr carries num_iters)
+        const LinReq r = lin_req(p, w, delta, bits, fsr, mode);
+        st = hip_status(launch_lin_delta_batch(1, &r, s), "lin step launch");
+        if (st) return st;
+    }
     if (p.kind == KIND_DIRECT_F32 || p.kind == KIND_PW_F32) {  // mode none: the weight as given, no pack
         if (!(phases & RUN_CONV)) return PO2Q_OK;
         if (!w) {
@@ -233,7 +261,8 @@ static int run_plan(const ConvPlan& p, const float* x, const float* w, const flo
         }
         return hip_status(launch_conv_f32s(p, x, w, bias, y, e.ps, e.pb, e.res, e.act, s), "conv launch");
     }
-    if ((phases & RUN_PACK) && L.nparts > 0) {
+    const bool do_pack = (phases & (RUN_PACK | RUN_PACK2)) != 0;
+    if (do_pack && L.nparts > 0) {
         st = hip_status(launch_absmax(w, nw, partial, L.nparts, s), "absmax launch");
         if (st) return st;
     }
@@ -250,9 +279,9 @@ static int run_plan(const ConvPlan& p, const float* x, const float* w, const flo
             q.hi = hi;
             q.mode = mode - 1;
         }
-        if ((phases & RUN_PACK) && !p.fp) {
+        if (do_pack && !p.fp) {
             st = hip_status(launch_pack_bf16x3(p, w, partial, L.nparts, bits, fsr, mode,
-                                               reinterpret_cast<uint16_t*>(packed), scale, s),
+                                               reinterpret_cast<uint16_t*>(packed), scale, s, delta),
                             "weight pack launch");
             if (st) return st;
         }
@@ -284,9 +313,9 @@ static int run_plan(const ConvPlan& p, const float* x, const float* w, const flo
         if (st || !e.any() || (fused_affine && !e.res)) return st;
         return hip_status(launch_epilogue(y, p.N, p.K, (int64_t)p.P * p.Q, e, fused_affine, s), "epilogue launch");
     }
-    if (phases & RUN_PACK) {
+    if (do_pack) {
         st = hip_status(
-            launch_pack_weights(p, w, partial, L.nparts, bits, fsr, mode, reinterpret_cast<float*>(packed), s),
+            launch_pack_weights(p, w, partial, L.nparts, bits, fsr, mode, reinterpret_cast<float*>(packed), s, delta),
             "weight pack launch");
         if (st) return st;
     }
@@ -331,7 +360,7 @@ int po2q_qconv2d_f32(const float* x, const float* w, const float* bias, float* y
                      int64_t W, int64_t K, int64_t R, int64_t S, int64_t stride_h, int64_t stride_w, int64_t pad_h,
                      int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t groups, int bits, int fsr, int mode,
                      int flags, void* workspace, size_t workspace_bytes, void* stream) {
-    int st = check_conv_args(x, w, y, workspace, mode, bits, flags);
+    int st = check_conv_args(x, w, y, workspace, mode, bits, flags, fsr);
     if (st) return st;
     ConvPlan p;
     if (!make_plan(p, N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, mode, bits, fsr,
@@ -346,7 +375,7 @@ int po2q_qconv2d_fused_f32(const float* x, const float* w, const float* bias, fl
                            int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t groups, int bits,
                            int fsr, int mode, int flags, const float* post_scale, const float* post_shift,
                            const float* residual, int act, void* workspace, size_t workspace_bytes, void* stream) {
-    int st = check_conv_args(x, w, y, workspace, mode, bits, flags);
+    int st = check_conv_args(x, w, y, workspace, mode, bits, flags, fsr);
     if (st) return st;
     if (act < PO2Q_ACT_NONE || act > PO2Q_ACT_SILU) {
         set_error("po2q: unknown activation " + std::to_string(act));
@@ -366,7 +395,7 @@ int po2q_qconv2d_autotune(const float* x, const float* w, const float* bias, flo
                           int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t groups, int bits,
                           int fsr, int mode, int flags, void* workspace, size_t workspace_bytes, void* stream,
                           char* buf, size_t len) {
-    int st = check_conv_args(x, w, y, workspace, mode, bits, flags);
+    int st = check_conv_args(x, w, y, workspace, mode, bits, flags, fsr);
     if (st) return st;
     std::vector<ConvPlan> cands;
     if (!plan_candidates(cands, N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, mode,
@@ -465,7 +494,7 @@ int po2q_qconv2d_f32_plan(int index, const float* x, const float* w, const float
                           int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w,
                           int64_t groups, int bits, int fsr, int mode, int flags, void* workspace,
                           size_t workspace_bytes, void* stream) {
-    int st = check_conv_args(x, w, y, workspace, mode, bits, flags);
+    int st = check_conv_args(x, w, y, workspace, mode, bits, flags, fsr);
     if (st) return st;
     std::vector<ConvPlan> cands;
     if (!plan_candidates(cands, N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, mode,
@@ -540,7 +569,7 @@ int po2q_qconv2d_pack_f32(int plan, const float* w, int64_t N, int64_t C, int64_
                           int64_t dil_h, int64_t dil_w, int64_t groups, int bits, int fsr, int mode, int flags,
                           void* workspace, size_t workspace_bytes, void* stream) {
     // the conv-argument checks of po2q_qconv2d_f32 (x and y are not touched here)
-    int st = check_conv_args(w, w, const_cast<float*>(w), workspace, mode, bits, flags);
+    int st = check_conv_args(w, w, const_cast<float*>(w), workspace, mode, bits, flags, fsr);
     if (st) return st;
     ConvPlan p;
     st = pick_split_plan(p, plan, N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, mode,
@@ -555,7 +584,7 @@ int po2q_qconv2d_packed_f32(int plan, const float* x, const float* bias, float* 
                             int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t groups, int bits,
                             int fsr, int mode, int flags, const void* workspace, size_t workspace_bytes,
                             void* stream) {
-    int st = check_conv_args(x, x, y, const_cast<void*>(workspace), mode, bits, flags);
+    int st = check_conv_args(x, x, y, const_cast<void*>(workspace), mode, bits, flags, fsr);
     if (st) return st;
     ConvPlan p;
     st = pick_split_plan(p, plan, N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, mode,
@@ -599,7 +628,7 @@ int po2q_qconv2d_plan_create(po2q_conv_plan** out, int index, int64_t N, int64_t
         return PO2Q_ERR_INVALID;
     }
     *out = nullptr;
-    if (!check_mode_bits(mode, bits, true)) return PO2Q_ERR_INVALID;
+    if (!check_mode_bits(mode, bits, true) || !check_lin_iters(mode, fsr)) return PO2Q_ERR_INVALID;
     if (flags < PO2Q_PREC_AUTO || flags > PO2Q_PREC_BF16X3) {
         set_error("po2q: unknown precision flag " + std::to_string(flags));
         return PO2Q_ERR_INVALID;
@@ -654,6 +683,29 @@ int po2q_qconv2d_plan_pack_batch(int n, const po2q_conv_plan* const* plans, cons
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     std::vector<PackReq> reqs;
+    // lin / lin+ plans: phase 1 (the per-channel steps) of every such tensor first, batched; their
+    // phase 2 rides the batched pack launch below, or runs as the plan's own pack launch
+    std::vector<LinReq> lins;
+    for (int i = 0; i < n; ++i) {
+        const po2q_conv_plan* h = plans[i];
+        if (!h || !is_lin_mode(h->mode)) continue;
+        if (!w[i] || !workspace[i]) {
+            set_error("po2q: pack batch: null plan, weight or workspace");
+            return PO2Q_ERR_INVALID;
+        }
+        const WsLayout L = ws_layout(h->p, h->mode);
+        if (workspace_bytes[i] < L.total) {
+            set_error("po2q: pack batch: workspace too small (need " + std::to_string(L.total) + " bytes)");
+            return PO2Q_ERR_WORKSPACE;
+        }
+        if (!plan_packs_weight(h->p, h->mode)) continue;
+        lins.push_back(lin_req(h->p, w[i], reinterpret_cast<float*>(reinterpret_cast<char*>(workspace[i]) + L.delta_off),
+                               h->bits, h->fsr, h->mode));
+    }
+    if (!lins.empty()) {
+        const int st = hip_status(launch_lin_delta_batch((int)lins.size(), lins.data(), s), "batched lin step launch");
+        if (st) return st;
+    }
     for (int i = 0; i < n; ++i) {
         const po2q_conv_plan* h = plans[i];
         if (!h || !w[i] || !workspace[i]) {
@@ -669,7 +721,8 @@ int po2q_qconv2d_plan_pack_batch(int n, const po2q_conv_plan* const* plans, cons
         if (!plan_packs_weight(p, h->mode)) continue;  // the conv stages its own weight / reads it as given
         if (!pack_batchable(p, h->mode) || L.nparts > 0) {  // its own pack launch(es), as po2q_qconv2d_pack_f32
             const int st = run_plan(p, nullptr, w[i], nullptr, nullptr, h->bits, h->fsr, h->mode, workspace[i],
-                                    workspace_bytes[i], s, ConvEpi{nullptr, nullptr, nullptr, 0}, RUN_PACK);
+                                    workspace_bytes[i], s, ConvEpi{nullptr, nullptr, nullptr, 0},
+                                    is_lin_mode(h->mode) ? RUN_PACK2 : RUN_PACK);
             if (st) return st;
             continue;
         }
@@ -677,6 +730,7 @@ int po2q_qconv2d_plan_pack_batch(int n, const po2q_conv_plan* const* plans, cons
         reqs.push_back(PackReq{&p, w[i], ws + L.packed_off, reinterpret_cast<float*>(ws + L.scale_off), h->bits, h->fsr,
                                h->mode});
         reqs.back().partial = reinterpret_cast<unsigned*>(ws);  // the layout's absmax partials (part_bytes)
+        if (is_lin_mode(h->mode)) reqs.back().delta = reinterpret_cast<const float*>(ws + L.delta_off);
     }
     if (reqs.empty()) return PO2Q_OK;
     return hip_status(launch_pack_batch((int)reqs.size(), reqs.data(), s), "batched weight pack launch");
@@ -735,6 +789,8 @@ static int ir_check(const po2q_conv_plan* e, const po2q_conv_plan* d, const po2q
         why = "the expand plan is not a pointwise bf16x3 conv producing the depthwise input";
     else if ((e && e->mode == PO2Q_MODE_NONE) || d->mode == PO2Q_MODE_NONE || p->mode == PO2Q_MODE_NONE)
         why = "mode none has no staged weights";
+    else if ((e && is_lin_mode(e->mode)) || is_lin_mode(d->mode) || is_lin_mode(p->mode))
+        why = "the block kernel does not take lin / lin+ plans";
     const int64_t Cin = e ? e->p.C : Ch;
     if (why.empty() && !ir_plan(*ip, N, Cin, H, W, Ch, Pj.K, S, e != nullptr))
         why = "no block geometry fits (channels not a multiple of 16, or too large)";

@@ -302,14 +302,44 @@ static bool plan_heuristic(ConvPlan& p, int mode, int bits, int fsr, int flags, 
             return true;
         }
     }
-    if (bf16x3_wanted(p, mode, flags)) {
+    // lin / lin+ (fsr carries num_iters): the bf16x3 kernels of the matching po2 problem when Q(w)
+    // is exact in bf16 (lin_bf16x3_ok), without the plans that stage the weight in the kernel (fp:
+    // their staging is the po2 quantizer; the stride-2 full-row kernel, vrx 5, has no other form).
+    // The planners only look at the exponent window, so they are asked about a one-level one.
+    const bool lin = is_lin_mode(mode);
+    if (lin && (fsr < 0 || bits < 1 || bits > 16)) {
+        set_error("po2q: lin / lin+ need 1 <= bits <= 16 and num_iters >= 0 (passed as fsr)");
+        return false;
+    }
+    if (lin && flags == 2 && !lin_bf16x3_ok(bits, fsr, p.groups)) {
+        set_error("po2q: bf16x3 precision for lin / lin+ needs groups == 1, bits <= 9 and num_iters >= 1");
+        return false;
+    }
+    const bool lin_x3 = lin && flags != 1 && lin_bf16x3_ok(bits, fsr, p.groups);
+    if (lin) {
+        mode = 1;
+        bits = 1;
+        fsr = 1;
+    }
+    auto drop_fused = [&](std::vector<PlanCand>& v) {
+        if (!lin) return;
+        v.erase(std::remove_if(v.begin(), v.end(),
+                               [](const PlanCand& c) {
+                                   return c.plan.fp || (c.plan.kind == KIND_BF16X3_ROWS && c.plan.vrx == 5);
+                               }),
+                v.end());
+    };
+    if (lin ? lin_x3 : bf16x3_wanted(p, mode, flags)) {
         std::vector<PlanCand> reg, dma;
         x3_candidates(p, mode, bits, fsr, reg);
+        drop_fused(reg);
         if (!reg.empty()) {
             const char* nd = getenv("PO2Q_NO_DMA");  // A/B knob: keep the register-staged kernel
             if (!(nd && nd[0] == '1')) x3p_candidates(p, dma);
+            drop_fused(dma);
             std::vector<PlanCand> rows;
             rows_candidates(p, mode, bits, fsr, rows);
+            drop_fused(rows);
             std::stable_sort(rows.begin(), rows.end(),
                              [](const PlanCand& u, const PlanCand& v) { return u.cost < v.cost; });
             p = (!dma.empty() && prefer_dma(p)) ? dma[0].plan : reg[0].plan;
@@ -319,11 +349,13 @@ static bool plan_heuristic(ConvPlan& p, int mode, int bits, int fsr, int flags, 
             // 1x1 / stride 1: the pointwise GEMM kernel (no halo, no LDS, fused epilogue)
             std::vector<PlanCand> pwc;
             pw_candidates(p, mode, bits, fsr, pwc);
+            drop_fused(pwc);
             if (!pwc.empty() && !tuning_knobs()) p = pwc[0].plan;
             // small images (CIFAR sizes): the LDS-resident block kernel; its candidates ride on
             // the pointwise list (the two never apply to the same shape)
             if (pwc.empty()) {
                 img_candidates(p, mode, bits, fsr, pwc);
+                drop_fused(pwc);
                 if (!pwc.empty() && p.W <= 32 && !tuning_knobs()) p = pwc[0].plan;
             }
             if (pw_out) *pw_out = std::move(pwc);

@@ -566,6 +566,10 @@ int po2q_qconv2d_chain_f32(const float* x, const float* const* w, const float* c
                            const float* const* post_scale, const float* const* post_shift, const int* act,
                            const int* res_from, int n_layers, int64_t N, int64_t C, int64_t H, int64_t W, int bits,
                            int fsr, int mode, float* y, void* workspace, size_t workspace_bytes, void* stream) {
+    if (po2q::is_lin_mode(mode)) {  // the multi-layer kernels stage po2 weights in-kernel
+        po2q::set_error("po2q: chain does not take the lin / lin+ modes");
+        return PO2Q_ERR_UNSUPPORTED;
+    }
     if (!chain_geom_ok(N, C, H, W, n_layers)) {
         set_error("po2q: chain needs C in {16, 32, 64}, W % 4 == 0, 1.." + std::to_string(kChainMax) +
                   " layers and a small image: its split planes in LDS ((H + 2)(W + 2) 6C bytes <= 160 KiB) and "

@@ -1292,6 +1292,10 @@ int po2q_qconv2d_pair_f32(const float* x, const float* w1, const float* w2, floa
                           int64_t H, int64_t W, int bits, int fsr, int mode, const float* bias1, const float* bias2,
                           const float* post_scale1, const float* post_shift1, int act1, const float* post_scale2,
                           const float* post_shift2, const float* residual, int act2, void* stream) {
+    if (po2q::is_lin_mode(mode)) {  // the multi-layer kernels stage po2 weights in-kernel
+        po2q::set_error("po2q: pair does not take the lin / lin+ modes");
+        return PO2Q_ERR_UNSUPPORTED;
+    }
     if (!pair_args_ok(N, C, H, W, bits, fsr, mode, act1, act2)) return PO2Q_ERR_INVALID;
     if (!x || !w1 || !w2 || !y) {
         po2q::set_error("po2q: null pointer");

@@ -525,6 +525,10 @@ int po2q_qconv2d_s2ds_f32(const float* x, const float* w, const float* wds, floa
                           int64_t C, int64_t H, int64_t W, int bits, int fsr, int mode, const float* post_scale,
                           const float* post_shift, int act, const float* post_scale_ds, const float* post_shift_ds,
                           void* stream) {
+    if (po2q::is_lin_mode(mode)) {  // the multi-layer kernels stage po2 weights in-kernel
+        po2q::set_error("po2q: s2ds does not take the lin / lin+ modes");
+        return PO2Q_ERR_UNSUPPORTED;
+    }
     if (!x || !w || !wds || !y || !yds) {
         po2q::set_error("po2q: s2ds: null pointer");
         return PO2Q_ERR_INVALID;

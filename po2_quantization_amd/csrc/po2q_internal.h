@@ -26,6 +26,14 @@ hipError_t launch_absmax(const float* w, int64_t n, unsigned* partial, int block
 hipError_t launch_quantize_plain(const float* w, int64_t n, const unsigned* partial, int nparts,
                                  int bits, int fsr, int mode, float* out, hipStream_t s);
 
+// the lin / lin+ conv modes (PO2Q_MODE_LIN / PO2Q_MODE_LIN_PLUS); their fsr argument is num_iters
+inline bool is_lin_mode(int mode) { return mode == 3 || mode == 4; }
+// bf16x3 eligibility of a lin problem: the step is a power of two after one refit and |q| <= 255
+// fits bf16's significand, so Q(w) is exact in bf16
+inline bool lin_bf16x3_ok(int bits, int num_iters, int groups) {
+    return groups == 1 && bits >= 1 && bits <= 9 && num_iters >= 1;
+}
+
 // Conv kinds
 enum ConvKind {
     KIND_MFMA_F32 = 0,
@@ -39,7 +47,8 @@ enum ConvKind {
     KIND_BF16X3_IMG = 8   // 3x3 / stride 1, small images: the block's rows resident in LDS (po2q_conv_img.hip)
 };
 
-// Every kind whose weight is packed as exact bf16 +-2^e fragments + one fp32 scale.
+// Every kind whose weight is packed as exact bf16 fragments (+-2^e for po2 / po2+, delta_c * q for
+// lin / lin+) + one fp32 scale.
 inline bool is_bf16x3_kind(int kind) {
     return kind == KIND_BF16X3 || kind == KIND_BF16X3_DMA || kind == KIND_BF16X3_ROWS || kind == KIND_BF16X3_PW ||
            kind == KIND_BF16X3_IMG;
@@ -145,13 +154,14 @@ hipError_t launch_conv_f32s(const ConvPlan& p, const float* x, const float* w, c
 
 // Pack (and quantize unless mode == 0) the weight into the plan's layout.
 hipError_t launch_pack_weights(const ConvPlan& p, const float* w, const unsigned* partial, int nparts,
-                               int bits, int fsr, int mode, float* packed, hipStream_t s);
+                               int bits, int fsr, int mode, float* packed, hipStream_t s,
+                               const float* delta = nullptr);
 
 // bf16x3: quantize + pack weights as exact bf16 +-2^e fragments, write the
 // scale multiplier to *scale_out.  nparts == 0: absmax is reduced in-kernel.
 hipError_t launch_pack_bf16x3(const ConvPlan& p, const float* w, const unsigned* partial, int nparts,
                               int bits, int fsr, int mode, uint16_t* packed, float* scale_out,
-                              hipStream_t s);
+                              hipStream_t s, const float* delta = nullptr);
 
 // One weight tensor of a batched pack: plan (a bf16x3 kind, or KIND_DEPTHWISE: the plain
 // quantized fp32 copy), weight, destination (bf16 fragments / fp32 copy), scale slot (bf16x3).
@@ -162,6 +172,7 @@ struct PackReq {
     float* scale;
     int bits, fsr, mode;
     unsigned* partial = nullptr;  // absmax_blocks(n) words of the plan's workspace (null: fused absmax only)
+    const float* delta = nullptr;  // lin / lin+: the Cg per-channel steps launch_lin_delta_batch wrote
 };
 // whether a plan's weight staging can join a batched pack (quantized, fused absmax size,
 // bf16x3 or depthwise kind)
@@ -231,5 +242,13 @@ hipError_t launch_quantize_dt(const T* w, T* out, int64_t n, int bits, int fsr, 
 // lin / lin+ quantizer (po2q_lin.hip): w, out [d0, d1, rs = d2*d3], one block per d1 channel
 hipError_t launch_quantize_lin(const float* w, float* out, int d0, int d1, int rs, int bits, int num_iters, int plus,
                                hipStream_t s);
+// Phase 1 of the lin conv modes: delta[c] = the step of channel c (launch_quantize_lin's arithmetic,
+// bit for bit) for n weight tensors, one launch per thread-count class (at most 3) and 84 tensors.
+struct LinReq {
+    const float* w;
+    float* delta;  // d1 floats
+    int d0, d1, rs, bits, num_iters, plus;
+};
+hipError_t launch_lin_delta_batch(int n, const LinReq* reqs, hipStream_t s);
 
 }  // namespace po2q

@@ -20,152 +20,104 @@
 #include <cstdint>
 
 #include "po2q_internal.h"
-#include "po2q_log2_table.h"
+#include "po2q_lin_dev.h"
 
 namespace po2q {
 
 namespace {
-
-constexpr int kLinMaxPer = 16;  // elements per thread held in VGPRs
-
-__device__ __forceinline__ float lin_qpf(float x, float d, float lim) {
-    float s = rintf(__fdiv_rn(x, d));
-    s = s < -lim ? -lim : (s > lim ? lim : s);  // NaN passes, as torch.clamp
-    return __fdiv_rn(__fmul_rn(d, s), d);
-}
-
-// 2 ** round(log2(v)) exactly as torch computes it in fp32
-__device__ __forceinline__ float lin_snap(float v) {
-    if (__builtin_isnan(v) || v < 0.0f) return __builtin_nanf("");
-    if (v == 0.0f) return 0.0f;
-    if (__builtin_isinf(v)) return v;
-    const uint32_t b = __float_as_uint(v);
-    int e;
-    if (b >= 0x00800000u) {
-        const int k = (int)(b >> 23) - 127;
-        e = k + (b >= po2q_l2r_thr[k - PO2Q_L2R_THR_KMIN] ? 1 : 0);
-    } else {
-        const int k = (31 - __builtin_clz(b)) - 149;
-        e = k + ((double)v >= ldexp(1.4142135623730951, k) ? 1 : 0);
-    }
-    return ldexpf(1.0f, e);
-}
-
-template <int NTH, typename T>
-__device__ __forceinline__ T lin_block_sum(T v, T* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();  // red may still be read by the previous reduction
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    T s = red[0];
-#pragma unroll
-    for (int i = 1; i < NTH / 64; ++i) s += red[i];  // fixed order
-    return s;
-}
 
 // NTH threads per channel; REG: the channel's elements fit in VGPRs (<= 16 NTH)
 template <int NTH, bool REG>
 __global__ __launch_bounds__(NTH) void quantize_lin_kernel(const float* __restrict__ w, float* __restrict__ out,
                                                                    int d0, int d1, int rs, int bits, int num_iters,
                                                                    int plus) {
-    __shared__ double redd[NTH / 64];
     const int c = blockIdx.x;
     const int m = d0 * rs;
     const float lim = (float)((1 << (bits - 1)) - 1);
-    const float levels = (float)((1 << bits) - 1);
     auto addr = [&](int i) { return ((int64_t)(i / rs) * d1 + c) * rs + i % rs; };
     float xr[REG ? kLinMaxPer : 1];
-    // ---- range of the channel (torch.max / torch.min over dims 0, 2, 3; NaN propagates)
-    float mx = -INFINITY, mn = INFINITY, nan = 0.0f;
-#pragma unroll
-    for (int u = 0; u < (REG ? kLinMaxPer : 1); ++u) xr[u] = 0.0f;
-    if constexpr (REG) {
-#pragma unroll
-        for (int u = 0; u < kLinMaxPer; ++u) {
-            const int i = threadIdx.x + u * NTH;
-            if (i < m) {
-                const float v = w[addr(i)];
-                xr[u] = v;
-                nan = __builtin_isnan(v) ? 1.0f : nan;
-                mx = v > mx ? v : mx;
-                mn = v < mn ? v : mn;
-            }
-        }
-    } else {
-        for (int i = threadIdx.x; i < m; i += NTH) {
-            const float v = w[addr(i)];
-            nan = __builtin_isnan(v) ? 1.0f : nan;
-            mx = v > mx ? v : mx;
-            mn = v < mn ? v : mn;
-        }
-    }
-    // max / min / any-NaN over the block (float shuffles; fmaxf is fine: NaN tracked apart)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        mn = fminf(mn, __shfl_xor(mn, o, 64));
-        nan = fmaxf(nan, __shfl_xor(nan, o, 64));
-    }
-    __shared__ float rmx[NTH / 64], rmn[NTH / 64], rnan[NTH / 64];
-    if ((threadIdx.x & 63) == 0) {
-        rmx[threadIdx.x >> 6] = mx;
-        rmn[threadIdx.x >> 6] = mn;
-        rnan[threadIdx.x >> 6] = nan;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NTH / 64; ++i) {
-        mx = fmaxf(mx, rmx[i]);
-        mn = fminf(mn, rmn[i]);
-        nan = fmaxf(nan, rnan[i]);
-    }
-    if (nan != 0.0f) mx = mn = __builtin_nanf("");
-    float delta = __fdiv_rn(__fsub_rn(mx, mn), levels);  // (max - min) / (2^bits - 1)
-    const float shrink = __fsqrt_rn(8.0f / 9.0f);          // torch.sqrt(torch.tensor(8/9))
-    for (int it = 0; it < num_iters; ++it) {
-        double qtw = 0.0, qtq = 0.0;
-        if constexpr (REG) {
-#pragma unroll
-            for (int u = 0; u < kLinMaxPer; ++u) {
-                const int i = threadIdx.x + u * NTH;
-                if (i < m) {
-                    const float q = lin_qpf(xr[u], delta, lim);
-                    qtw += (double)q * (double)xr[u];
-                    qtq += (double)q * (double)q;
-                }
-            }
-        } else {
-            for (int i = threadIdx.x; i < m; i += NTH) {
-                const float x = w[addr(i)];
-                const float q = lin_qpf(x, delta, lim);
-                qtw += (double)q * (double)x;
-                qtq += (double)q * (double)q;
-            }
-        }
-        qtw = lin_block_sum<NTH>(qtw, redd);
-        qtq = lin_block_sum<NTH>(qtq, redd);
-        float nd = __fdiv_rn((float)qtw, (float)qtq);
-        if (plus) nd = __fmul_rn(shrink, nd);
-        delta = lin_snap(nd);
-    }
+    const float delta = lin_channel_delta<NTH, REG>(w, d0, d1, rs, c, bits, num_iters, plus, xr);
     // ---- out = (qpf(w, delta) / delta) * delta
     if constexpr (REG) {
 #pragma unroll
         for (int u = 0; u < kLinMaxPer; ++u) {
             const int i = threadIdx.x + u * NTH;
-            if (i < m) out[addr(i)] = __fmul_rn(lin_qpf(xr[u], delta, lim), delta);
+            if (i < m) out[addr(i)] = lin_value(xr[u], delta, lim);
         }
     } else {
         for (int i = threadIdx.x; i < m; i += NTH) {
             const int64_t a = addr(i);
-            out[a] = __fmul_rn(lin_qpf(w[a], delta, lim), delta);
+            out[a] = lin_value(w[a], delta, lim);
         }
     }
 }
 
+// Phase 1 of the lin conv modes' weight pack: the step of every (tensor, input channel) of a batch
+// of weight tensors in one launch, one workgroup per channel, delta[c] into the tensor's workspace.
+// blk0 is the prefix table that maps blockIdx.x to its job (block b serves channel b - blk0 of the
+// last job with blk0 <= b).  Same body as quantize_lin_kernel: the same bits.
+struct LinJob {
+    const float* w;
+    float* delta;
+    int d0, d1, rs, bits, num_iters, plus, blk0, pad;
+};
+constexpr int kLinBatch = 84;  // 84 x 48-byte jobs + the count: under the 4 KB kernel-argument limit
+struct LinBatch {
+    LinJob job[kLinBatch];
+    int n;
+};
+static_assert(sizeof(LinBatch) <= 4096, "lin_delta_batch_kernel's arguments must fit the 4 KB kernel-argument limit");
+
+template <int NTH, bool REG>
+__global__ __launch_bounds__(NTH) void lin_delta_batch_kernel(LinBatch B) {
+    int j = 0;
+    while (j + 1 < B.n && (int)blockIdx.x >= B.job[j + 1].blk0) ++j;  // block-uniform
+    const LinJob& J = B.job[j];
+    const int c = (int)blockIdx.x - J.blk0;
+    if (c >= J.d1) return;  // block-uniform (never taken: the grid is the sum of the d1)
+    float xr[REG ? kLinMaxPer : 1];
+    const float delta = lin_channel_delta<NTH, REG>(J.w, J.d0, J.d1, J.rs, c, J.bits, J.num_iters, J.plus, xr);
+    if (threadIdx.x == 0) J.delta[c] = delta;
+}
+
+// thread-count class of a channel of m elements: launch_quantize_lin's choice, so the fixed-order
+// sums (and with them the step) are the plain quantizer's
+int lin_class(int m) { return m <= 256 * kLinMaxPer ? 0 : (m <= 1024 * kLinMaxPer ? 1 : 2); }
+
 }  // namespace
+
+hipError_t launch_lin_delta_batch(int n, const LinReq* reqs, hipStream_t s) {
+    for (int cls = 0; cls < 3; ++cls) {
+        LinBatch B;
+        B.n = 0;
+        int blocks = 0;
+        auto flush = [&]() -> hipError_t {
+            if (B.n == 0) return hipSuccess;
+            if (cls == 0)
+                hipLaunchKernelGGL((lin_delta_batch_kernel<256, true>), dim3((unsigned)blocks), dim3(256), 0, s, B);
+            else if (cls == 1)
+                hipLaunchKernelGGL((lin_delta_batch_kernel<1024, true>), dim3((unsigned)blocks), dim3(1024), 0, s, B);
+            else
+                hipLaunchKernelGGL((lin_delta_batch_kernel<1024, false>), dim3((unsigned)blocks), dim3(1024), 0, s, B);
+            B.n = 0;
+            blocks = 0;
+            return hipGetLastError();
+        };
+        for (int i = 0; i < n; ++i) {
+            const LinReq& r = reqs[i];
+            if (lin_class(r.d0 * r.rs) != cls) continue;
+            B.job[B.n++] = LinJob{r.w, r.delta, r.d0, r.d1, r.rs, r.bits, r.num_iters, r.plus, blocks, 0};
+            blocks += r.d1;
+            if (B.n == kLinBatch) {
+                const hipError_t e = flush();
+                if (e != hipSuccess) return e;
+            }
+        }
+        const hipError_t e = flush();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 
 hipError_t launch_quantize_lin(const float* w, float* out, int d0, int d1, int rs, int bits, int num_iters, int plus,
                                hipStream_t s) {

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "po2q_internal.h"
+#include "po2q_lin_dev.h"
 #include "po2q_quant_dev.h"
 
 namespace po2q {
@@ -95,9 +96,29 @@ __global__ __launch_bounds__(1024) void quantize_plain_fused_kernel(const float*
         out[i] = quantize_elem(w[i], scale, mode, lo, hi);
 }
 
+// lin / lin+ (phase 2 of the lin conv modes, po2q_lin.hip has phase 1): the plain quantized copy
+// [K][1][R][S] a depthwise plan reads.  The tensor is one dim-1 channel: its step is delta[0].
+__global__ __launch_bounds__(1024) void quantize_lin_plain_kernel(const float* __restrict__ w, int n,
+                                                                  const float* __restrict__ delta, float lim,
+                                                                  float* __restrict__ out) {
+    const float d = delta[0];
+    for (int i = blockIdx.x * 1024 + threadIdx.x; i < n; i += gridDim.x * 1024) out[i] = lin_value(w[i], d, lim);
+}
+
 static inline void clamp_window(int bits, int fsr, int& lo, int& hi) {
     lo = fsr - (1 << (bits - 1));
     hi = fsr - 1;
+}
+
+// the (lo, hi) kernel arguments of a pack: the exponent window, or for lin / lin+ (0, the clamp
+// limit 2^(bits-1) - 1 of the integer level)
+static inline void pack_window(int bits, int fsr, int mode, int& lo, int& hi) {
+    if (is_lin_mode(mode)) {
+        lo = 0;
+        hi = (1 << (bits - 1)) - 1;
+    } else {
+        clamp_window(bits, fsr, lo, hi);
+    }
 }
 
 static int grid_for(int64_t n) {
@@ -129,10 +150,12 @@ struct PackGeom {
 __global__ __launch_bounds__(kThreads) void pack_mfma_f32_kernel(const float* __restrict__ w,
                                                                  const unsigned* __restrict__ partial,
                                                                  int nparts, int lo, int hi, int mode,
-                                                                 PackGeom pg, float* __restrict__ packed) {
+                                                                 PackGeom pg, float* __restrict__ packed,
+                                                                 const float* __restrict__ delta) {
     __shared__ unsigned red4[4];
     float scale = 1.0f;
-    if (mode >= 0) scale = fold_scale(partial, nparts, red4);
+    const bool lin = mode >= 2;  // lin / lin+: the per-channel steps delta[Cg] (phase 1), lim = hi
+    if (mode >= 0 && !lin) scale = fold_scale(partial, nparts, red4);
     const int64_t stride = (int64_t)gridDim.x * kThreads;
     for (int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x; j < pg.total; j += stride) {
         int64_t t = j;
@@ -152,7 +175,7 @@ __global__ __launch_bounds__(kThreads) void pack_mfma_f32_kernel(const float* __
         if (kk < pg.Kg && c < pg.Cg) {
             const int64_t k = (int64_t)g * pg.Kg + kk;
             const float x = w[((k * pg.Cg + c) * pg.R + r) * pg.S + s];
-            v = (mode >= 0) ? quantize_elem(x, scale, mode, lo, hi) : x;
+            v = lin ? lin_value(x, delta[c], (float)hi) : (mode >= 0) ? quantize_elem(x, scale, mode, lo, hi) : x;
         }
         packed[j] = v;
     }
@@ -206,23 +229,35 @@ __device__ __forceinline__ unsigned fused_absmax_bits(const float* __restrict__ 
 
 // The pack of one weight tensor by block `bid` of `nb` (pack_bf16x3_kernel: one tensor per
 // launch; pack_batch_kernel: one tensor per blockIdx.y).
+// LIN (the lin / lin+ conv modes): the value is Q(w) itself for the channel's step delta[c] of
+// phase 1 (lin_value, lim = hi), a bf16 number of at most 8 significant bits when the step is a
+// power of two and bits <= 9, so its high 16 bits are all of it; a NaN stays a NaN; the multiplier is 1.
+template <bool LIN>
 __device__ __forceinline__ void pack_bf16x3_body(const float* __restrict__ w, int64_t n,
                                                  const unsigned* __restrict__ partial, int nparts, int lo, int hi,
                                                  int mode, const PackX3& pg, uint16_t* __restrict__ packed,
-                                                 float* __restrict__ scale_out, int bid, int nb) {
-    __shared__ unsigned red[kPackThreads / 64];
-    __shared__ unsigned thr[PO2Q_THR_COUNT];
-    for (int i = threadIdx.x; i < PO2Q_THR_COUNT; i += kPackThreads) thr[i] = po2q_thr[mode > 0 ? 1 : 0][i];
-    unsigned m = 0u;
-    if (nparts > 0) {
-        for (int i = threadIdx.x; i < nparts; i += kPackThreads) m = max(m, partial[i]);
-    } else {  // fused absmax: every block reduces the whole (small, L2-resident) weight tensor
-        m = fused_absmax_bits(w, n);
+                                                 float* __restrict__ scale_out, int bid, int nb,
+                                                 const float* __restrict__ delta = nullptr) {
+    __shared__ unsigned red[LIN ? 1 : kPackThreads / 64];
+    __shared__ unsigned thr[LIN ? 1 : PO2Q_THR_COUNT];
+    float scale = 1.0f;
+    bool fin = false;
+    const float lim = (float)hi;
+    if constexpr (LIN) {
+        if (bid == 0 && threadIdx.x == 0) *scale_out = 1.0f;
+    } else {
+        for (int i = threadIdx.x; i < PO2Q_THR_COUNT; i += kPackThreads) thr[i] = po2q_thr[mode > 0 ? 1 : 0][i];
+        unsigned m = 0u;
+        if (nparts > 0) {
+            for (int i = threadIdx.x; i < nparts; i += kPackThreads) m = max(m, partial[i]);
+        } else {  // fused absmax: every block reduces the whole (small, L2-resident) weight tensor
+            m = fused_absmax_bits(w, n);
+        }
+        m = block_max_u32<kPackThreads / 64>(m, red);
+        scale = __uint_as_float(m);
+        fin = (m > 0u) && (m < 0x7f800000u);
+        if (bid == 0 && threadIdx.x == 0) *scale_out = fin ? scale : 1.0f;
     }
-    m = block_max_u32<kPackThreads / 64>(m, red);
-    const float scale = __uint_as_float(m);
-    const bool fin = (m > 0u) && (m < 0x7f800000u);
-    if (bid == 0 && threadIdx.x == 0) *scale_out = fin ? scale : 1.0f;
     // one 16-byte B fragment slot (8 consecutive k = 8 consecutive input channels of
     // one tap, one output channel) per thread and iteration; 32-bit index math
     const int OCT = pg.CC >> 3;
@@ -280,7 +315,12 @@ __device__ __forceinline__ void pack_bf16x3_body(const float* __restrict__ w, in
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int c = c0 + e;
-            h[e] = (ok && c < pg.C) ? pack_one(w[(k * pg.C + c) * RS + tapoff], scale, fin, mode, lo, hi, thr) : 0u;
+            if constexpr (LIN)
+                h[e] = (ok && c < pg.C)
+                           ? bf16_bits_keep_nan(lin_value(w[(k * pg.C + c) * RS + tapoff], delta[c], lim))
+                           : 0u;
+            else
+                h[e] = (ok && c < pg.C) ? pack_one(w[(k * pg.C + c) * RS + tapoff], scale, fin, mode, lo, hi, thr) : 0u;
         }
         out[j] = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
     }
@@ -290,8 +330,14 @@ __global__ __launch_bounds__(kPackThreads) void pack_bf16x3_kernel(const float* 
                                                                const unsigned* __restrict__ partial,
                                                                int nparts, int lo, int hi, int mode,
                                                                PackX3 pg, uint16_t* __restrict__ packed,
-                                                               float* __restrict__ scale_out) {
-    pack_bf16x3_body(w, n, partial, nparts, lo, hi, mode, pg, packed, scale_out, (int)blockIdx.x, (int)gridDim.x);
+                                                               float* __restrict__ scale_out,
+                                                               const float* __restrict__ delta) {
+    if (mode >= 2)  // lin / lin+
+        pack_bf16x3_body<true>(w, n, partial, nparts, lo, hi, mode, pg, packed, scale_out, (int)blockIdx.x,
+                               (int)gridDim.x, delta);
+    else
+        pack_bf16x3_body<false>(w, n, partial, nparts, lo, hi, mode, pg, packed, scale_out, (int)blockIdx.x,
+                                (int)gridDim.x);
 }
 
 // Up to kPackBatch weight tensors quantized + packed in one launch (blockIdx.y = tensor):
@@ -302,7 +348,10 @@ struct PackJob {
     const float* w;
     void* packed;
     float* scale;
-    const unsigned* partial;  // nparts > 0: max|w| from these absmax partials (absmax_batch_kernel)
+    union {
+        const unsigned* partial;  // nparts > 0: max|w| from these absmax partials (absmax_batch_kernel)
+        const float* delta;       // lin / lin+ (mode >= 2): the per-channel steps of phase 1; lim = hi
+    };
     int64_t n;
     int lo, hi, mode, nb, plain, nparts;
     PackX3 pg;
@@ -358,6 +407,13 @@ __global__ __launch_bounds__(256) void absmax_batch_kernel(AbsBatch B) {
 __global__ __launch_bounds__(kPackThreads) void pack_batch_kernel(PackBatch B) {
     const PackJob& j = B.job[blockIdx.y];
     if ((int)blockIdx.x >= j.nb) return;  // block-uniform
+    if (j.plain && j.mode >= 2) {  // lin / lin+ depthwise copy: one channel, step delta[0]
+        const float d = j.delta[0], lim = (float)j.hi;
+        float* out = reinterpret_cast<float*>(j.packed);
+        for (int i = blockIdx.x * kPackThreads + threadIdx.x; i < (int)j.n; i += j.nb * kPackThreads)
+            out[i] = lin_value(j.w[i], d, lim);
+        return;
+    }
     if (j.plain) {
         __shared__ unsigned red[kPackThreads / 64];
         unsigned m0 = 0u;
@@ -373,8 +429,12 @@ __global__ __launch_bounds__(kPackThreads) void pack_batch_kernel(PackBatch B) {
             out[i] = quantize_elem(j.w[i], scale, j.mode, j.lo, j.hi);
         return;
     }
-    pack_bf16x3_body(j.w, j.n, j.partial, j.nparts, j.lo, j.hi, j.mode, j.pg, reinterpret_cast<uint16_t*>(j.packed),
-                     j.scale, (int)blockIdx.x, j.nb);
+    if (j.mode >= 2)
+        pack_bf16x3_body<true>(j.w, j.n, nullptr, 0, j.lo, j.hi, j.mode, j.pg, reinterpret_cast<uint16_t*>(j.packed),
+                               j.scale, (int)blockIdx.x, j.nb, j.delta);
+    else
+        pack_bf16x3_body<false>(j.w, j.n, j.partial, j.nparts, j.lo, j.hi, j.mode, j.pg,
+                                reinterpret_cast<uint16_t*>(j.packed), j.scale, (int)blockIdx.x, j.nb);
 }
 
 static PackX3 pack_geom(const ConvPlan& p) {
@@ -393,7 +453,7 @@ static int pack_blocks(const PackX3& pg) {
 
 bool pack_batchable(const ConvPlan& p, int mode) {
     const int64_t n = (int64_t)p.K * p.Cg * p.R * p.S;
-    if (mode == 0 || n > kFusedAbsmaxMax) return false;
+    if (mode == 0 || n > kFusedAbsmaxMax) return false;  // (the lin modes need no absmax; the same sizes ride)
     return is_bf16x3_kind(p.kind) || p.kind == KIND_DEPTHWISE;
 }
 
@@ -412,14 +472,18 @@ hipError_t launch_pack_batch(int n, const PackReq* reqs, hipStream_t s) {
             const ConvPlan& p = *r.plan;
             PackJob& j = B.job[i];
             int lo, hi;
-            clamp_window(r.bits, r.fsr, lo, hi);
+            pack_window(r.bits, r.fsr, r.mode, lo, hi);
             j.w = r.w;
             j.packed = r.packed;
             j.scale = r.scale;
             j.n = (int64_t)p.K * p.Cg * p.R * p.S;
-            j.nparts = (r.partial && j.n > kTwoPhaseAbsmax) ? (int)((j.n + kAbsChunk - 1) / kAbsChunk) : 0;
-            j.partial = r.partial;
-            A.job[i] = AbsJob{r.w, r.partial, j.n, j.nparts};
+            const bool lin = is_lin_mode(r.mode);
+            j.nparts = (!lin && r.partial && j.n > kTwoPhaseAbsmax) ? (int)((j.n + kAbsChunk - 1) / kAbsChunk) : 0;
+            if (lin)
+                j.delta = r.delta;
+            else
+                j.partial = r.partial;
+            A.job[i] = AbsJob{r.w, lin ? nullptr : r.partial, j.n, j.nparts};
             npmax = std::max(npmax, j.nparts);
             j.lo = lo; j.hi = hi; j.mode = r.mode - 1;
             j.plain = p.kind == KIND_DEPTHWISE ? 1 : 0;
@@ -453,24 +517,31 @@ hipError_t launch_pack_bf16x3_batch(int n, const ConvPlan* const* plans, const f
 }
 
 hipError_t launch_pack_bf16x3(const ConvPlan& p, const float* w, const unsigned* partial, int nparts, int bits,
-                              int fsr, int mode, uint16_t* packed, float* scale_out, hipStream_t s) {
+                              int fsr, int mode, uint16_t* packed, float* scale_out, hipStream_t s,
+                              const float* delta) {
     int lo, hi;
-    clamp_window(bits, fsr, lo, hi);
+    pack_window(bits, fsr, mode, lo, hi);
     const PackX3 pg = pack_geom(p);
     const int b = pack_blocks(pg);
     const int64_t n = (int64_t)p.K * p.Cg * p.R * p.S;
     hipLaunchKernelGGL(pack_bf16x3_kernel, dim3((unsigned)b), dim3(kPackThreads), 0, s, w, n, partial, nparts, lo, hi,
-                       mode - 1, pg, packed, scale_out);
+                       mode - 1, pg, packed, scale_out, delta);
     return hipGetLastError();
 }
 
 hipError_t launch_pack_weights(const ConvPlan& p, const float* w, const unsigned* partial, int nparts, int bits,
-                               int fsr, int mode, float* packed, hipStream_t s) {
+                               int fsr, int mode, float* packed, hipStream_t s, const float* delta) {
     int lo = 0, hi = 0;
-    if (mode != 0) clamp_window(bits, fsr, lo, hi);
+    if (mode != 0) pack_window(bits, fsr, mode, lo, hi);
     if (p.kind == KIND_DEPTHWISE) {  // depthwise: plain [K][1][R][S] quantized copy
         const int64_t n = (int64_t)p.K * p.Cg * p.R * p.S;
         if (mode == 0) return hipMemcpyAsync(packed, w, n * sizeof(float), hipMemcpyDeviceToDevice, s);
+        if (is_lin_mode(mode)) {
+            const int b = (int)std::min<int64_t>(64, (n + 4095) / 4096);
+            hipLaunchKernelGGL(quantize_lin_plain_kernel, dim3(b), dim3(1024), 0, s, w, (int)n, delta, (float)hi,
+                               packed);
+            return hipGetLastError();
+        }
         if (nparts == 0) {  // fused absmax (small tensor)
             const int b = (int)std::min<int64_t>(8, (n + 4095) / 4096);
             hipLaunchKernelGGL(quantize_plain_fused_kernel, dim3(b), dim3(1024), 0, s, w, (int)n, lo, hi, mode - 1,
@@ -486,7 +557,7 @@ hipError_t launch_pack_weights(const ConvPlan& p, const float* w, const unsigned
     pg.nchunks = p.nchunks; pg.kblocks = p.kblocks; pg.steps = p.steps; pg.groups = p.groups;
     pg.total = p.packed_floats;
     hipLaunchKernelGGL(pack_mfma_f32_kernel, dim3(grid_for(pg.total)), dim3(kThreads), 0, s, w, partial, nparts,
-                       lo, hi, mode - 1, pg, packed);
+                       lo, hi, mode - 1, pg, packed, delta);
     return hipGetLastError();
 }
 

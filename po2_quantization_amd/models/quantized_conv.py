@@ -8,7 +8,10 @@ same get_quantization_error().  forward() runs the fused libpo2q path:
       -> one native call: absmax + quantize + pack + conv kernels
   quantize_fn None
       -> native conv of the raw weight (reference :37-38)
-  any other quantize_fn (e.g. lin / lin+ or a user Function)
+  quantize_fn in {LinearPowerOfTwoQuantizer, LinearPowerOfTwoPlusQuantizer}
+      -> one native call in mode "lin" / "lin+": per-channel step + pack + conv kernels (bf16x3
+         for groups == 1 and bits <= 9); NATIVE_LIN = False restores the route below
+  any other quantize_fn (a user Function)
       -> qw = quantize_fn.apply(weight, bits), then the native conv of qw
 
 Backward (QAT) keeps the reference's semantics: straight-through estimator on
@@ -35,7 +38,25 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..utils.quantizers import NATIVE_MODES
+from ..utils.quantizers import LIN_NATIVE_MODES, LIN_NUM_ITERS, NATIVE_MODES
+
+
+# False: lin / lin+ layers quantize with their own launch and run the conv as mode "none" (the route
+# every non-native quantize_fn takes; for A/B measurements)
+NATIVE_LIN = True
+
+
+def native_mode(quantize_fn):
+    """The libpo2q conv mode of a quantizer class: "po2" / "po2+", "lin" / "lin+" (NATIVE_LIN), else None."""
+    mode = NATIVE_MODES.get(quantize_fn)
+    if mode is None and NATIVE_LIN:
+        mode = LIN_NATIVE_MODES.get(quantize_fn)
+    return mode
+
+
+def _fsr(mode):
+    """The C ABI's fsr argument: 1 (the reference's default) for po2 / po2+, num_iters for the lin modes."""
+    return LIN_NUM_ITERS if mode in ("lin", "lin+") else 1
 
 
 # False: every backward is one aten.convolution_backward of Q(w) (for A/B measurements)
@@ -48,7 +69,7 @@ ATEN_BACKWARD_CALLS = 0
 class _QConv2dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, stride, padding, dilation, groups, bits, mode, precision):
-        y = _lib.qconv2d(x, weight, bias, stride, padding, dilation, groups, bits, mode, 1, precision)
+        y = _lib.qconv2d(x, weight, bias, stride, padding, dilation, groups, bits, mode, _fsr(mode), precision)
         ctx.save_for_backward(x, weight, bias)
         ctx.conf = (stride, padding, dilation, groups, bits, mode)
         ctx.precision = precision
@@ -62,7 +83,10 @@ class _QConv2dFn(torch.autograd.Function):
                     inserted between its pixels (po2q_dilate_f32; strided layers) with the
                     weight transposed (K <-> C within each group) and flipped, padding
                     dil * (R - 1) - pad: Q commutes with that permutation, so these are the same
-                    exact PO2 weights; dense, grouped and depthwise layers alike;
+                    exact PO2 weights; dense, grouped and depthwise layers alike.  The lin
+                    quantizers are per dim-1 channel and do not commute with the K <-> C transpose:
+                    their Q(w) is computed once (quantize_lin), transposed and flipped, and the
+                    conv runs as mode "none";
           weight -- po2q_qconv2d_wgrad_f32: fp32 MFMA for dense 1x1 / 3x3 layers, a fixed-order
                     fp32 reduction for depthwise layers;
           bias   -- sum of gy over N, P, Q.
@@ -79,16 +103,18 @@ class _QConv2dFn(torch.autograd.Function):
         native_x = NATIVE_BACKWARD and need_x and padl[0] >= 0 and padl[1] >= 0
         native_w = NATIVE_BACKWARD and need_w and _lib.wgrad_supported(weight.shape, groups)
         gx = gw = gb = None
+        lin = mode in ("lin", "lin+")
+        qw = _lib.quantize_lin(weight.detach(), bits, mode == "lin+", LIN_NUM_ITERS) if lin and (need_x or need_w) else None
         if native_x:
             G = int(groups)
-            wt = weight.detach().view(G, K // G, Cg, R, S).transpose(1, 2).reshape(G * Cg, K // G, R, S)
+            wt = (qw if lin else weight.detach()).view(G, K // G, Cg, R, S).transpose(1, 2).reshape(G * Cg, K // G, R, S)
             wt = wt.flip(2, 3).contiguous()
             src = gy
             if tuple(st) != (1, 1):
                 H, W = x.shape[2], x.shape[3]
                 size = (H + 2 * pad[0] - dil[0] * (R - 1), W + 2 * pad[1] - dil[1] * (S - 1))
                 src = _lib.dilate(gy, st, size)
-            gx = _lib.qconv2d(src, wt, None, 1, padl, dil, G, bits, mode, 1, ctx.precision)
+            gx = _lib.qconv2d(src, wt, None, 1, padl, dil, G, bits, "none" if lin else mode, 1, ctx.precision)
         if native_w:
             gw = _lib.conv_wgrad(x, gy, weight.shape, stride, padding, dilation, groups)
         if need_b:
@@ -97,7 +123,8 @@ class _QConv2dFn(torch.autograd.Function):
         if rest_x or rest_w:
             global ATEN_BACKWARD_CALLS
             ATEN_BACKWARD_CALLS += 1
-            qw = weight if mode == "none" else _lib.quantize(weight, bits, mode)
+            if not lin:
+                qw = weight if mode == "none" else _lib.quantize(weight, bits, mode)
             rx, rw, _ = torch.ops.aten.convolution_backward(
                 gy, x, qw, None, list(stride), list(padding), list(dilation), False, [0, 0], groups,
                 [rest_x, rest_w, False])
@@ -209,8 +236,8 @@ class _ForwardPacks:
             groups.setdefault(conf, []).append((m, g, plan))
         for conf, items in groups.items():
             bits, mode, prec = conf
-            ws = _lib.pack_batch([(m.weight, g[0], g[1], g[2], g[3], g[4]) for m, g, _ in items], bits, mode, 1,
-                                 prec, plans=[pl for _, _, pl in items])
+            ws = _lib.pack_batch([(m.weight, g[0], g[1], g[2], g[3], g[4]) for m, g, _ in items], bits, mode,
+                                 _fsr(mode), prec, plans=[pl for _, _, pl in items])
             for (m, g, pl), w in zip(items, ws):
                 self.ws[id(m)] = (g, m.weight, w, pl, conf)
 
@@ -220,7 +247,7 @@ class _ForwardPacks:
         hit = self.ws.get(id(conv))
         if hit is None or hit[0] != g or hit[1] is not weight or hit[2].numel() == 0:
             return None
-        if hit[4] != (conv.bits, NATIVE_MODES.get(conv.quantize_fn), conv.precision):
+        if hit[4] != (conv.bits, native_mode(conv.quantize_fn), conv.precision):
             return None
         return hit
 
@@ -238,7 +265,7 @@ def batched_packs(model, x):
         return
     # the record holds which layers read a packed weight and with which plan; it depends on the
     # layers' quantizer settings and precision as much as on the input shape
-    confs = tuple((m.bits, NATIVE_MODES.get(m.quantize_fn), m.precision) for m in model.modules()
+    confs = tuple((m.bits, native_mode(m.quantize_fn), m.precision) for m in model.modules()
                   if isinstance(m, QuantizedConv2d))
     key = (tuple(x.shape), x.device, INFERENCE_FUSION, IR_FUSION, confs)
     rec = _RECORDS.get(model)
@@ -313,8 +340,8 @@ class QuantizedConv2d(nn.Conv2d):
             return self._torch_forward(input)
         if self.quantize_fn is None:
             return self._native(input, self.weight, "none")
-        mode = NATIVE_MODES.get(self.quantize_fn)
-        if mode is not None:
+        mode = native_mode(self.quantize_fn)
+        if mode is not None and not (mode in ("lin", "lin+") and input.dtype != torch.float32):
             return self._native(input, self.weight, mode)
         quantized_weight = self.quantize_fn.apply(self.weight, self.bits)
         return self._native(input, quantized_weight, "none")
@@ -327,9 +354,9 @@ class QuantizedConv2d(nn.Conv2d):
             return _torch_epilogue(self(input), bn, act, residual)
         if self.padding_mode != "zeros":
             raise RuntimeError("po2q: only padding_mode='zeros' is supported (the reference uses the default)")
-        mode = "none" if self.quantize_fn is None else NATIVE_MODES.get(self.quantize_fn)
+        mode = "none" if self.quantize_fn is None else native_mode(self.quantize_fn)
         weight = self.weight
-        if mode is None:  # a non-native quantizer (lin / lin+ / user Function): quantize first
+        if mode is None:  # a non-native quantizer (a user Function; lin / lin+ without NATIVE_LIN): quantize first
             weight = self.quantize_fn.apply(self.weight, self.bits)
             mode = "none"
         ps, pb = fold_bn(bn) if bn is not None else (None, None)
@@ -342,11 +369,11 @@ class QuantizedConv2d(nn.Conv2d):
                 hit = sess.lookup(self, g, weight)
                 if hit is not None:
                     return _lib.qconv2d_packed(input, weight, hit[2], self.bias, g[1], g[2], g[3], g[4], self.bits,
-                                               mode, 1, self.precision, post_scale=ps, post_shift=pb,
+                                               mode, _fsr(mode), self.precision, post_scale=ps, post_shift=pb,
                                                residual=residual, act=act or "none", plan=hit[3])
         return _lib.qconv2d_fused(input, weight, self.bias, self.stride, self._padding(input), self.dilation,
-                                  self.groups, self.bits, mode, 1, self.precision, post_scale=ps, post_shift=pb,
-                                  residual=residual, act=act or "none")
+                                  self.groups, self.bits, mode, _fsr(mode), self.precision, post_scale=ps,
+                                  post_shift=pb, residual=residual, act=act or "none")
 
     def get_quantization_error(self):
         # reference quantized_conv.py:40-45
@@ -460,7 +487,8 @@ def _ir_spec(seq):
     if ok:
         convs = [g[0] for g in groups]
         conf = {(c.bits, c.quantize_fn, c.precision) for c in convs}
-        ok = (len(conf) == 1 and NATIVE_MODES.get(convs[0].quantize_fn) is not None
+        # (po2 / po2+ only: the block kernel does not take lin / lin+ packs)
+        ok = (len(conf) == 1 and NATIVE_MODES.get(convs[0].quantize_fn) in ("po2", "po2+")
               and all(c.bias is None and c.padding_mode == "zeros" and not isinstance(c.padding, str)
                       and tuple(c.dilation) == (1, 1) for c in convs))
     if ok:

@@ -17,7 +17,8 @@ reference (:34-36, :54-56).
 LinearPowerOfTwo(Plus)Quantizer (utils/quantizers.py:59-136)
 run on the native per-channel kernel po2q_quantize_lin_f32 (po2q_lin.hip) for fp32
 HIP 4-D weights, and on _lib.restated_quantize_lin (the reference's torch ops) for
-CPU tensors.
+CPU tensors.  Inside a QuantizedConv2d on HIP they are the native conv modes "lin" /
+"lin+" (LIN_NATIVE_MODES): quantize + pack + conv in the library, no separate launch.
 """
 from typing import Callable, Optional
 
@@ -77,6 +78,15 @@ class LinearPowerOfTwoPlusQuantizer(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_output):
         return grad_output, None, None
+
+
+# lin / lin+ classes -> the native conv mode of libpo2q (PO2Q_MODE_LIN / PO2Q_MODE_LIN_PLUS).  Kept
+# apart from NATIVE_MODES: the multi-layer kernels (pair, s2ds, chain, inverted residual) gate on
+# NATIVE_MODES and stage po2 weights themselves, so lin only ever joins the single-conv and
+# batched-pack paths (QuantizedConv2d.forward / .fused).
+LIN_NATIVE_MODES = {LinearPowerOfTwoQuantizer: "lin", LinearPowerOfTwoPlusQuantizer: "lin+"}
+# quantize_fn.apply(weight, bits) runs the quantizers' default num_iters
+LIN_NUM_ITERS = 10
 
 
 def quantize_model(model: torch.nn.Module, quantizer: Optional[Callable[..., None]], bits: int) -> float:
