@@ -5,8 +5,9 @@
  * plain pointers, sizes and a HIP stream handle; no torch types.  Every entry
  * point is asynchronous on `stream` (no host synchronisation, no allocation):
  * the caller owns every buffer, including the workspace whose size the
- * matching *_workspace_bytes() function returns.  All device pointers are
- * device-resident fp32, contiguous NCHW / [K, C/groups, R, S].
+ * matching *_workspace_bytes() function returns.  Device pointers are
+ * device-resident, contiguous NCHW / [K, C/groups, R, S]; fp32 except where an entry's name
+ * says otherwise (_f64; _bf16: uint16_t bf16 bit patterns, po2q_quantize_bf16 and po2q_qconv2d_bf16).
  *
  * Return value: PO2Q_OK (0) or a PO2Q_ERR_* code; po2q_last_error() then
  * holds a message (thread-local).  Invalid arguments are rejected before any
@@ -133,6 +134,45 @@ int po2q_qconv2d_f32(const float* x, const float* w, const float* bias, float* y
                      int64_t dil_h, int64_t dil_w, int64_t groups,
                      int bits, int fsr, int mode, int flags,
                      void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * The same forward with every tensor bf16, as the reference computes it for a model in bf16
+ * (model.bfloat16(): F.conv2d(x, quantize_fn.apply(w, bits), bias, ...) on bf16 tensors).
+ * x, w, bias (or NULL) and y are bf16 bit patterns: x, y contiguous NCHW, w [K, C/groups, R, S].
+ * mode: PO2Q_MODE_NONE, PO2Q_MODE_PO2 or PO2Q_MODE_PO2_PLUS; PO2Q_MODE_LIN / _LIN_PLUS return
+ * PO2Q_ERR_UNSUPPORTED (there is no bf16 lin quantizer).
+ * Q(w) is exactly what po2q_quantize_bf16 returns for the whole weight tensor (torch's bf16
+ * arithmetic, scale = max|w| as a bf16, an all-zero or NaN weight gives NaN): one device body
+ * serves both.  Q(w) is itself a bf16 number and goes into the matrix unit as it is (no scale
+ * factor): y = bf16_rne(acc + float(bias[k])) with acc the fp32 accumulation of the exact products
+ * x * Q(w), one v_mfma_f32_16x16x32_bf16 per k-step.  Padded taps read zeros, never a pixel.
+ * Range limit: exact while every nonzero |x| and |Q(w)| is a normal bf16 (>= 2^-126); below that
+ * the matrix unit may flush the operand to zero.
+ * groups == 1: any C, K, R, S, stride, padding, dilation po2q_qconv2d_f32 takes.  Depthwise
+ * (groups == C == K) with R, S <= 5: a direct kernel, fp32 FMAs in tap order.  Any other groups:
+ * PO2Q_ERR_UNSUPPORTED.  Arguments are validated as by po2q_qconv2d_f32 (same messages).
+ * At most two launches precede the conv (max|w|, then quantize + pack; mode none: the pack alone).
+ * The tile comes from a heuristic; po2q_qconv2d_bf16_describe names the kernel and its tile
+ * ("kind=bf16x1 ..." / "kind=dw_bf16 ...").  po2q_qconv2d_bf16_workspace_bytes returns 0 (and sets
+ * the error) for arguments the entry rejects.
+ */
+size_t po2q_qconv2d_bf16_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W,
+                                         int64_t K, int64_t R, int64_t S,
+                                         int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
+                                         int64_t dil_h, int64_t dil_w, int64_t groups,
+                                         int bits, int fsr, int mode);
+int po2q_qconv2d_bf16(const uint16_t* x, const uint16_t* w, const uint16_t* bias, uint16_t* y,
+                      int64_t N, int64_t C, int64_t H, int64_t W,
+                      int64_t K, int64_t R, int64_t S,
+                      int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
+                      int64_t dil_h, int64_t dil_w, int64_t groups,
+                      int bits, int fsr, int mode,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int po2q_qconv2d_bf16_describe(int64_t N, int64_t C, int64_t H, int64_t W,
+                               int64_t K, int64_t R, int64_t S,
+                               int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
+                               int64_t dil_h, int64_t dil_w, int64_t groups,
+                               int bits, int fsr, int mode, char* buf, size_t len);
 
 /*
  * Conv forward with its eval-mode epilogue fused into the launch:

@@ -9,7 +9,7 @@ planning / tuning / diagnostic entry points, the two-enqueue SplitConv, and ever
 PO2Q_LIB points at another build of libpo2q.so (diagnostic builds).
 
 fp32 HIP tensors always run the native kernels: a missing library raises, there is no
-torch fallback for them.  The PO2 / PO2+ quantizer also takes fp64 and bf16 HIP tensors natively
+torch fallback for them.  bf16 HIP tensors have the forward-only qconv2d_bf16 (po2q_qconv2d_bf16).  The PO2 / PO2+ quantizer also takes fp64 and bf16 HIP tensors natively
 (the reference preserves dtype); other inputs (CPU tensors, fp16, ...) take
 restated_quantize, the reference formula written as torch ops in the input's dtype and device.
 """
@@ -69,6 +69,9 @@ EXPORTS = (
     "po2q_qconv2d_ir_supported",
     "po2q_qconv2d_ir_shape_supported",
     "po2q_qconv2d_ir_f32",
+    "po2q_qconv2d_bf16_workspace_bytes",
+    "po2q_qconv2d_bf16",
+    "po2q_qconv2d_bf16_describe",
 )
 
 # Kernel autotuning on the first call per conv problem, the counterpart of
@@ -188,6 +191,12 @@ def load():
     L.po2q_qconv2d_chain_workspace_bytes.argtypes = [i64] * 4 + [i32]
     L.po2q_qconv2d_chain_f32.restype = i32
     L.po2q_qconv2d_chain_f32.argtypes = ([p] * 7 + [i32] + [i64] * 4 + [i32] * 3 + [p, p, sz, p])
+    L.po2q_qconv2d_bf16_workspace_bytes.restype = sz
+    L.po2q_qconv2d_bf16_workspace_bytes.argtypes = [i64] * 14 + [i32, i32, i32]
+    L.po2q_qconv2d_bf16.restype = i32
+    L.po2q_qconv2d_bf16.argtypes = [p, p, p, p] + [i64] * 14 + [i32, i32, i32, p, sz, p]
+    L.po2q_qconv2d_bf16_describe.restype = i32
+    L.po2q_qconv2d_bf16_describe.argtypes = [i64] * 14 + [i32, i32, i32, ctypes.c_char_p, sz]
     _lib = L
     return L
 
@@ -386,6 +395,73 @@ def qconv2d(x, w, bias=None, stride=1, padding=0, dilation=1, groups=1, bits=4, 
             _check(L.po2q_qconv2d_f32(xc.data_ptr(), wc.data_ptr(), bp, y.data_ptr(), *key,
                                       ws.data_ptr(), ws.numel(), _stream(xc.device)))
     return y
+
+
+def _require_hip_bf16(t, what):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("po2q: %s must be a torch.Tensor" % what)
+    if t.device.type != "cuda":
+        raise Po2qError("po2q: %s must be a HIP device tensor (got %s); the po2q ops have no CPU path"
+                        % (what, t.device))
+    if t.dtype != torch.bfloat16:
+        raise Po2qError("po2q: %s must be bfloat16 (got %s); the bf16 conv takes input, weight and bias of one dtype"
+                        % (what, t.dtype))
+
+
+def qconv2d_bf16(x, w, bias=None, stride=1, padding=0, dilation=1, groups=1, bits=4, mode="po2", fsr=1):
+    """The reference's forward with every tensor bf16 (model.bfloat16(): F.conv2d(x, Q(w), bias, ...) on
+    bf16 tensors, models/quantized_conv.py:32-38) as one native call (po2q_qconv2d_bf16): Q(w) exactly
+    quantize(w) in bf16, one bf16 MFMA pass with fp32 accumulation, bf16 out.  mode "none" / "po2" /
+    "po2+"; groups 1 or depthwise.  Forward only."""
+    _require_hip_bf16(x, "input")
+    _require_hip_bf16(w, "weight")
+    if bias is not None:
+        _require_hip_bf16(bias, "bias")
+    if x.dim() != 4 or w.dim() != 4:
+        raise Po2qError("po2q: expected 4-D input and weight, got %d-D and %d-D" % (x.dim(), w.dim()))
+    if x.device != w.device or (bias is not None and bias.device != x.device):
+        raise Po2qError("po2q: input, weight and bias must be on the same device")
+    N, C, H, W = x.shape
+    K, Cg, R, S = w.shape
+    if Cg * groups != C:
+        raise Po2qError("po2q: Given groups=%d, weight of size %s, expected input%s to have %d channels, but got "
+                        "%d channels instead" % (groups, list(w.shape), list(x.shape), Cg * groups, C))
+    sh, sw = _pair(stride)
+    ph, pw = _pair(padding)
+    dh, dw = _pair(dilation)
+    mode_id = MODES[mode]
+    args = (N, C, H, W, K, R, S, sh, sw, ph, pw, dh, dw, int(groups))
+    P = (H + 2 * ph - dh * (R - 1) - 1) // sh + 1 if sh > 0 else 0
+    Q = (W + 2 * pw - dw * (S - 1) - 1) // sw + 1 if sw > 0 else 0
+    yshape = (N, K, max(P, 0), max(Q, 0))
+    if N == 0:  # an empty batch: torch's F.conv2d returns an empty output
+        return torch.empty(yshape, dtype=torch.bfloat16, device=x.device)
+    O = ops()
+    if O is not None:
+        return _op_call(O.qconv2d_bf16, x, w, bias, [sh, sw], [ph, pw], [dh, dw], int(groups), int(bits), mode_id,
+                        int(fsr))
+    L = load()
+    xc, wc = x.contiguous(), w.contiguous()
+    bc = bias.contiguous() if bias is not None else None
+    with torch.cuda.device(xc.device):
+        nbytes = L.po2q_qconv2d_bf16_workspace_bytes(*args, int(bits), int(fsr), mode_id)
+        if nbytes == 0:
+            _check(1)
+        y = torch.empty(yshape, dtype=torch.bfloat16, device=xc.device)
+        ws = _workspace(nbytes, xc.device)
+        _check(L.po2q_qconv2d_bf16(xc.data_ptr(), wc.data_ptr(), bc.data_ptr() if bc is not None else None,
+                                   y.data_ptr(), *args, int(bits), int(fsr), mode_id, ws.data_ptr(), ws.numel(),
+                                   _stream(xc.device)))
+    return y
+
+
+def describe_bf16(N, C, H, W, K, R, S, stride=1, padding=0, dilation=1, groups=1, bits=4, mode="po2", fsr=1):
+    """The kernel and tile qconv2d_bf16 runs for this shape (diagnostic text)."""
+    L = load()
+    buf = ctypes.create_string_buffer(512)
+    _check(L.po2q_qconv2d_bf16_describe(N, C, H, W, K, R, S, *_pair(stride), *_pair(padding), *_pair(dilation),
+                                        int(groups), int(bits), int(fsr), MODES[mode], buf, 512))
+    return buf.value.decode()
 
 
 def qconv2d_fused(x, w, bias=None, stride=1, padding=0, dilation=1, groups=1, bits=4, mode="po2", fsr=1,

@@ -610,6 +610,68 @@ int po2q_qconv2d_describe(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K,
     return PO2Q_OK;
 }
 
+// ------------------------------------------------------------------ bf16 conv --
+// The checks the three bf16 entries share, after the pointer checks: mode and bits as
+// po2q_qconv2d_f32, the geometry with its messages, then what the bf16 kernels do not take.
+static int b16_resolve(ConvPlan& p, int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t R, int64_t S,
+                       int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t groups,
+                       int bits, int mode) {
+    if (!check_mode_bits(mode, bits, true)) return PO2Q_ERR_INVALID;
+    if (!plan_geometry(p, N, C, H, W, K, R, S, sh, sw, ph, pw, dh, dw, groups)) return PO2Q_ERR_INVALID;
+    if (is_lin_mode(mode)) {
+        set_error("po2q: the bf16 conv has no lin / lin+ mode (there is no bf16 lin quantizer)");
+        return PO2Q_ERR_UNSUPPORTED;
+    }
+    return b16_plan(p);
+}
+
+size_t po2q_qconv2d_bf16_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t R,
+                                         int64_t S, int64_t stride_h, int64_t stride_w, int64_t pad_h,
+                                         int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t groups, int bits,
+                                         int fsr, int mode) {
+    ConvPlan p;
+    if (b16_resolve(p, N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, bits, mode))
+        return 0;
+    return b16_workspace_bytes(p);
+}
+
+int po2q_qconv2d_bf16(const uint16_t* x, const uint16_t* w, const uint16_t* bias, uint16_t* y, int64_t N, int64_t C,
+                      int64_t H, int64_t W, int64_t K, int64_t R, int64_t S, int64_t stride_h, int64_t stride_w,
+                      int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t groups, int bits, int fsr,
+                      int mode, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!check_mode_bits(mode, bits, true)) return PO2Q_ERR_INVALID;
+    if (!x || !w || !y || !workspace) {
+        set_error("po2q: null pointer");
+        return PO2Q_ERR_INVALID;
+    }
+    ConvPlan p;
+    const int st =
+        b16_resolve(p, N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, bits, mode);
+    if (st) return st;
+    const size_t need = b16_workspace_bytes(p);
+    if (workspace_bytes < need) {
+        set_error("po2q: conv workspace too small (need " + std::to_string(need) + " bytes)");
+        return PO2Q_ERR_WORKSPACE;
+    }
+    return hip_status(b16_run(p, x, w, bias, y, bits, fsr, mode, workspace, reinterpret_cast<hipStream_t>(stream)),
+                      "bf16 conv launch");
+}
+
+int po2q_qconv2d_bf16_describe(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t R, int64_t S,
+                               int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h,
+                               int64_t dil_w, int64_t groups, int bits, int fsr, int mode, char* buf, size_t len) {
+    if (!buf || len == 0) {
+        set_error("po2q: describe needs a buffer");
+        return PO2Q_ERR_INVALID;
+    }
+    ConvPlan p;
+    const int st =
+        b16_resolve(p, N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, bits, mode);
+    if (st) return st;
+    b16_describe(p, buf, len);
+    return PO2Q_OK;
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------ plan handles --

@@ -203,9 +203,8 @@ hipError_t launch_conv_depthwise_epi(const ConvPlan& p, const float* x, const fl
 static int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // Geometry validation (the reference's F.conv2d error conditions) and derived sizes.
-static bool plan_geometry(ConvPlan& p, int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t R,
-                          int64_t S, int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw,
-                          int64_t groups) {
+bool plan_geometry(ConvPlan& p, int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t R, int64_t S,
+                   int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t groups) {
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0 || R <= 0 || S <= 0 || groups <= 0) {
         set_error("po2q: all sizes must be positive");
         return false;

@@ -44,7 +44,9 @@ enum ConvKind {
     KIND_BF16X3_PW = 5,  // 1x1 / stride 1 GEMM kernel (po2q_conv_pw.hip)
     KIND_DIRECT_F32 = 6,  // unquantized 3-channel stems, direct fp32 (po2q_conv_f32s.hip)
     KIND_PW_F32 = 7,      // unquantized 1x1 convs, fp32 MFMA GEMM (po2q_conv_f32s.hip)
-    KIND_BF16X3_IMG = 8   // 3x3 / stride 1, small images: the block's rows resident in LDS (po2q_conv_img.hip)
+    KIND_BF16X3_IMG = 8,  // 3x3 / stride 1, small images: the block's rows resident in LDS (po2q_conv_img.hip)
+    KIND_BF16X1 = 9,      // bf16 in / out, one bf16 MFMA pass (po2q_conv_b16.hip; po2q_qconv2d_bf16 only)
+    KIND_DW_BF16 = 10     // bf16 in / out depthwise, direct (po2q_conv_b16.hip; po2q_qconv2d_bf16 only)
 };
 
 // Every kind whose weight is packed as exact bf16 fragments (+-2^e for po2 / po2+, delta_c * q for
@@ -81,6 +83,11 @@ struct ConvPlan {
     size_t lds_bytes;
     int64_t blocks;
 };
+
+// Geometry validation (the reference's F.conv2d error conditions) and the derived sizes of p; false
+// with the error set.
+bool plan_geometry(ConvPlan& p, int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t R, int64_t S,
+                   int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t groups);
 
 // Default plan for a conv: the autotuned plan when po2q_qconv2d_autotune has
 // measured this problem in this process, else the planners' heuristic choice.
@@ -238,6 +245,16 @@ hipError_t pairw_launch(const float* x, const float* w1, const float* w2, float*
 template <typename T>
 hipError_t launch_quantize_dt(const T* w, T* out, int64_t n, int bits, int fsr, int mode, uint64_t* partial,
                               int nparts, hipStream_t s);
+
+// bf16 conv (po2q_conv_b16.hip): x, w, bias, y as bf16 bit patterns.  b16_plan fills the tile of a
+// validated geometry (heuristic only; kind KIND_BF16X1 or KIND_DW_BF16) and returns 0 or the
+// PO2Q_ERR_* code with the error set; b16_run enqueues max|w| (quantized modes), the quantize +
+// pack and the conv.
+int b16_plan(ConvPlan& p);
+size_t b16_workspace_bytes(const ConvPlan& p);
+void b16_describe(const ConvPlan& p, char* buf, size_t len);
+hipError_t b16_run(const ConvPlan& p, const uint16_t* x, const uint16_t* w, const uint16_t* bias, uint16_t* y,
+                   int bits, int fsr, int mode, void* workspace, hipStream_t s);
 
 // lin / lin+ quantizer (po2q_lin.hip): w, out [d0, d1, rs = d2*d3], one block per d1 channel
 hipError_t launch_quantize_lin(const float* w, float* out, int d0, int d1, int rs, int bits, int num_iters, int plus,

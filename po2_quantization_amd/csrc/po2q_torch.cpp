@@ -25,6 +25,8 @@
 //   po2q::qconv2d_ir     a whole inverted-residual block (expand 1x1 -> depthwise 3x3 -> project
 //                        1x1, BN / ReLU6 / identity shortcut) in one launch from the three layers'
 //                        packed workspaces (mobilenet.py:53-134, mobile_vit.py:131-239)
+//   po2q::qconv2d_bf16   QuantizedConv2d.forward of a model in bf16 (model.bfloat16()): every tensor
+//                        bf16, one bf16 MFMA pass (po2q_qconv2d_bf16); forward only
 // Meta kernels give the output shapes (FX / torch.compile tracing, fake tensors).
 // Errors are TORCH_CHECK -> RuntimeError, as F.conv2d raises for bad arguments.
 #include <ATen/ATen.h>
@@ -232,6 +234,69 @@ at::Tensor qconv2d_fused(const at::Tensor& x, const at::Tensor& w, const c10::op
     TORCH_CHECK(act >= 0 && act <= 3, "po2q: unknown activation ", act);
     return qconv2d_impl(x, w, bias, stride, padding, dilation, groups, bits, mode, fsr, prec, plan, autotune,
                         post_scale, post_shift, residual, act);
+}
+
+// ---- bf16 forward (po2q_qconv2d_bf16): every tensor bf16, forward only ----------------------
+void check_hip_bf16(const at::Tensor& t, const char* what) {
+    TORCH_CHECK(t.is_cuda(), "po2q: ", what, " must be a HIP device tensor (got ", t.device(),
+                "); the po2q ops have no CPU path");
+    TORCH_CHECK(t.scalar_type() == at::kBFloat16, "po2q: ", what, " must be bfloat16 (got ", t.scalar_type(),
+                "); the bf16 conv takes input, weight and bias of one dtype");
+}
+
+std::vector<int64_t> conv_out_shape(const at::Tensor& x, const at::Tensor& w, at::IntArrayRef stride,
+                                    at::IntArrayRef padding, at::IntArrayRef dilation) {
+    TORCH_CHECK(x.dim() == 4 && w.dim() == 4, "po2q: expected 4-D input and weight, got ", x.dim(), "-D and ",
+                w.dim(), "-D");
+    const int64_t P = (x.size(2) + 2 * pick(padding, 0, "padding") - pick(dilation, 0, "dilation") * (w.size(2) - 1) -
+                       1) / pick(stride, 0, "stride") + 1;
+    const int64_t Q = (x.size(3) + 2 * pick(padding, 1, "padding") - pick(dilation, 1, "dilation") * (w.size(3) - 1) -
+                       1) / pick(stride, 1, "stride") + 1;
+    return {x.size(0), w.size(0), std::max<int64_t>(P, 0), std::max<int64_t>(Q, 0)};
+}
+
+at::Tensor qconv2d_bf16(const at::Tensor& x_, const at::Tensor& w_, const c10::optional<at::Tensor>& bias_,
+                        at::IntArrayRef stride, at::IntArrayRef padding, at::IntArrayRef dilation, int64_t groups,
+                        int64_t bits, int64_t mode, int64_t fsr) {
+    check_hip_bf16(x_, "input");
+    check_hip_bf16(w_, "weight");
+    const std::vector<int64_t> yshape = conv_out_shape(x_, w_, stride, padding, dilation);
+    TORCH_CHECK(x_.device() == w_.device(), "po2q: input and weight must be on the same device");
+    c10::optional<at::Tensor> bias;
+    if (bias_.has_value()) {
+        check_hip_bf16(*bias_, "bias");
+        TORCH_CHECK(bias_->device() == x_.device(), "po2q: bias must be on the input's device");
+        TORCH_CHECK(bias_->numel() == w_.size(0), "po2q: bias must have ", w_.size(0), " elements");
+        bias = bias_->contiguous();
+    }
+    TORCH_CHECK(groups > 0, "po2q: non-positive groups is not supported");
+    TORCH_CHECK(w_.size(1) * groups == x_.size(1), "po2q: Given groups=", groups, ", weight of size ", w_.sizes(),
+                ", expected input", x_.sizes(), " to have ", w_.size(1) * groups, " channels, but got ", x_.size(1),
+                " channels instead");
+    const DeviceGuard guard(x_.device());
+    const at::Tensor x = x_.contiguous(), w = w_.contiguous();
+    at::Tensor y = at::empty(yshape, x.options());
+    if (yshape[0] == 0) return y;  // an empty batch: torch's F.conv2d returns an empty output
+    const int64_t g[14] = {x.size(0), x.size(1), x.size(2), x.size(3), w.size(0), w.size(2), w.size(3),
+                           pick(stride, 0, "stride"), pick(stride, 1, "stride"), pick(padding, 0, "padding"),
+                           pick(padding, 1, "padding"), pick(dilation, 0, "dilation"), pick(dilation, 1, "dilation"),
+                           groups};
+    const size_t wsb = po2q_qconv2d_bf16_workspace_bytes(g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9],
+                                                         g[10], g[11], g[12], g[13], (int)bits, (int)fsr, (int)mode);
+    TORCH_CHECK(wsb > 0, last_error());
+    at::Tensor ws = at::empty({(int64_t)wsb}, x.options().dtype(at::kByte));
+    auto ptr = [](const at::Tensor& t) { return reinterpret_cast<uint16_t*>(t.data_ptr()); };
+    const int st = po2q_qconv2d_bf16(ptr(x), ptr(w), bias.has_value() ? ptr(*bias) : nullptr, ptr(y), g[0], g[1], g[2],
+                                     g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11], g[12], g[13], (int)bits,
+                                     (int)fsr, (int)mode, ws.data_ptr(), wsb, stream_of(x));
+    TORCH_CHECK(st == 0, last_error());
+    return y;
+}
+
+at::Tensor qconv2d_bf16_meta(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>&,
+                             at::IntArrayRef stride, at::IntArrayRef padding, at::IntArrayRef dilation, int64_t,
+                             int64_t, int64_t, int64_t) {
+    return at::empty(conv_out_shape(x, w, stride, padding, dilation), x.options().dtype(at::kBFloat16));
 }
 
 at::Tensor quantize(const at::Tensor& w_, int64_t bits, int64_t mode, int64_t fsr) {
@@ -790,6 +855,8 @@ TORCH_LIBRARY(po2q, m) {
           "int stride, int bits, int mode, int fsr=1, int precision=0, Tensor? ps1=None, Tensor? pb1=None, "
           "int act1=0, Tensor? ps2=None, Tensor? pb2=None, int act2=0, Tensor? ps3=None, Tensor? pb3=None, "
           "Tensor? residual=None, int act3=0, int[] plans=[]) -> Tensor");
+    m.def("qconv2d_bf16(Tensor x, Tensor w, Tensor? bias, int[] stride, int[] padding, int[] dilation, int groups, "
+          "int bits, int mode, int fsr=1) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(po2q, CUDA, m) {  // the HIP device (PyTorch-ROCm dispatches HIP tensors under CUDA)
@@ -805,6 +872,7 @@ TORCH_LIBRARY_IMPL(po2q, CUDA, m) {  // the HIP device (PyTorch-ROCm dispatches 
     m.impl("qconv2d_pack_batch", &qconv2d_pack_batch);
     m.impl("qconv2d_packed", &qconv2d_packed);
     m.impl("qconv2d_ir", &qconv2d_ir);
+    m.impl("qconv2d_bf16", &qconv2d_bf16);
 }
 
 TORCH_LIBRARY_IMPL(po2q, Meta, m) {
@@ -820,4 +888,5 @@ TORCH_LIBRARY_IMPL(po2q, Meta, m) {
     m.impl("qconv2d_pack_batch", &qconv2d_pack_batch_meta);
     m.impl("qconv2d_packed", &qconv2d_packed_meta);
     m.impl("qconv2d_ir", &qconv2d_ir_meta);
+    m.impl("qconv2d_bf16", &qconv2d_bf16_meta);
 }

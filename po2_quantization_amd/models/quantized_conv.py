@@ -18,7 +18,9 @@ Backward (QAT) keeps the reference's semantics: straight-through estimator on
 the weight (quantizers.py:34-36), conv gradients of the quantized weight -- the input
 gradient through the native conv kernels (strided layers on zero-inserted dy), the weight
 gradient through the native fp32 wgrad kernels, dense and depthwise (_QConv2dFn.backward).
-HIP inputs must be fp32 (anything else raises; there is no silent fallback on the GPU).  CPU
+HIP inputs are fp32, or bf16 for the forward-only native bf16 conv (po2q_qconv2d_bf16: po2 / po2+ /
+no quantizer, groups 1 or depthwise; BatchNorm, residual and activation then run as the module
+sequence does); anything else raises, there is no silent fallback on the GPU.  CPU
 inputs take the reference's own torch arithmetic (`_torch_forward`: the product's restated
 quantizers + F.conv2d, never the oracle, never libpo2q), as the reference runs on any device.
 
@@ -131,6 +133,26 @@ class _QConv2dFn(torch.autograd.Function):
             gx = rx if rest_x else gx
             gw = rw if rest_w else gw
         return gx, gw, gb, None, None, None, None, None, None, None
+
+
+def _require_no_grad(*tensors):
+    """The bf16 path has no backward: refuse to run where autograd would record it."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise _lib.Po2qError("po2q: the bf16 conv is forward-only (input, weight or bias requires grad): run it "
+                             "under torch.no_grad(), or train in fp32")
+
+
+def _plain_conv_bf16(conv, x):
+    """An unquantized nn.Conv2d on a bf16 HIP input: the native bf16 entry in mode "none".  The module's
+    forward is not called, so its forward hooks are run here, as calling the module would."""
+    _require_no_grad(x, conv.weight, conv.bias)
+    y = _lib.qconv2d_bf16(x, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups, 4,
+                          "none", 1)
+    for hook in list(conv._forward_hooks.values()):
+        out = hook(conv, (x,), y)
+        if out is not None:
+            y = out
+    return y
 
 
 _ACT_NAMES = {nn.ReLU: "relu", nn.ReLU6: "relu6", nn.SiLU: "silu"}
@@ -334,10 +356,30 @@ class QuantizedConv2d(nn.Conv2d):
             return self._conv_forward(input, self.weight, self.bias)
         return self._conv_forward(input, self.quantize_fn.apply(self.weight, self.bits), self.bias)
 
+    def _bf16_forward(self, input):
+        """A bf16 HIP input: the native bf16 entry (po2q_qconv2d_bf16), forward only.  po2 / po2+ are its
+        native modes; any other quantize_fn is applied first (lin / lin+ have no bf16 kernel and raise there,
+        a user Function returns its own Q(w)) and the conv runs as mode "none"."""
+        if self.padding_mode != "zeros":
+            raise RuntimeError("po2q: only padding_mode='zeros' is supported (the reference uses the default)")
+        _require_no_grad(input, self.weight, self.bias)
+        weight, mode = self.weight, "none"
+        if self.quantize_fn is not None:
+            mode = NATIVE_MODES.get(self.quantize_fn)
+            if mode is None:
+                weight, mode = self.quantize_fn.apply(self.weight, self.bits), "none"
+        unbatched = input.dim() == 3
+        x = input.unsqueeze(0) if unbatched else input
+        y = _lib.qconv2d_bf16(x, weight, self.bias, self.stride, self._padding(x), self.dilation, self.groups,
+                              self.bits, mode, 1)
+        return y.squeeze(0) if unbatched else y
+
     def forward(self, input):
         # reference quantized_conv.py:32-38
         if not input.is_cuda:
             return self._torch_forward(input)
+        if input.dtype == torch.bfloat16:
+            return self._bf16_forward(input)
         if self.quantize_fn is None:
             return self._native(input, self.weight, "none")
         mode = native_mode(self.quantize_fn)
@@ -351,6 +393,8 @@ class QuantizedConv2d(nn.Conv2d):
         can_fuse).  bn: the following eval BatchNorm or None; act: None | 'relu' |
         'relu6' | 'silu'."""
         if not input.is_cuda:  # CPU: the reference's module sequence (conv -> bn -> + residual -> act)
+            return _torch_epilogue(self(input), bn, act, residual)
+        if input.dtype == torch.bfloat16:  # the native bf16 conv, then the module sequence's own bf16 roundings
             return _torch_epilogue(self(input), bn, act, residual)
         if self.padding_mode != "zeros":
             raise RuntimeError("po2q: only padding_mode='zeros' is supported (the reference uses the default)")
@@ -390,6 +434,9 @@ def plain_conv(conv, x):
     the native fp32 kernels with the native backward (_QConv2dFn, mode "none": exact fp32 products,
     the weight gradient from the fixed-order wgrad kernels, so a training step is deterministic run to
     run); any other input runs the module itself."""
+    if (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and conv.padding_mode == "zeros"
+            and not isinstance(conv.padding, str)):
+        return _plain_conv_bf16(conv, x)
     if (not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4) or conv.padding_mode != "zeros"
             or isinstance(conv.padding, str)):
         return conv(x)
@@ -405,13 +452,16 @@ def plain_conv_fused(conv, x, bn=None, act=None, residual=None):
         return _torch_epilogue(conv(x), bn, act, residual)
     if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
         raise RuntimeError("po2q: fused plain conv needs numeric zero padding")
+    if x.dtype == torch.bfloat16:  # the native bf16 conv, then the module sequence's own bf16 roundings
+        return _torch_epilogue(_plain_conv_bf16(conv, x), bn, act, residual)
     ps, pb = fold_bn(bn) if bn is not None else (None, None)
     return _lib.qconv2d_fused(x, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups, 4,
                               "none", 1, "auto", post_scale=ps, post_shift=pb, residual=residual, act=act or "none")
 
 
 def _native_ok(x):
-    return x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+    # (bf16: the fused calls run the native bf16 conv, then BatchNorm / activation as the modules do)
+    return x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and x.dim() == 4
 
 
 def fusable_sequence(seq):

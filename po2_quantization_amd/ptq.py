@@ -49,13 +49,17 @@ def init() -> None:
     torch.backends.cudnn.benchmark = True
 
 
-def test_model(model: nn.Module, test_loader: Iterable, device) -> float:
-    """Top-1 accuracy over (images, labels) batches (test.py:34-47)."""
+DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+
+
+def test_model(model: nn.Module, test_loader: Iterable, device, dtype=torch.float32) -> float:
+    """Top-1 accuracy over (images, labels) batches (test.py:34-47); the images are cast to dtype
+    (the model's: --dtype bf16 evaluates a model.bfloat16())."""
     correct, total = 0, 0
     model.eval()
     with torch.no_grad():
         for images, labels in test_loader:
-            images, labels = images.to(device), labels.to(device)
+            images, labels = images.to(device=device, dtype=dtype), labels.to(device)
             outputs = model(images)
             _, predicted = torch.max(outputs.data, 1)
             total += labels.size(0)
@@ -81,32 +85,42 @@ def _qat_error(csv_path: str) -> float:
 
 
 def evaluate_seed(model_type: str, num_classes: int, image_size, seed_dir: str, test_loader: Sequence,
-                  device, skip_qat: bool = False, bits: Sequence[int] = bits_to_try, log=print) -> List[Row]:
-    """One seed's rows in the reference's order (test.py:98-159)."""
+                  device, skip_qat: bool = False, bits: Sequence[int] = bits_to_try, log=print,
+                  dtype=torch.float32) -> List[Row]:
+    """One seed's rows in the reference's order (test.py:98-159).  dtype torch.bfloat16: every model is
+    cast with .bfloat16() after loading, so quantize_model runs in bf16 as the reference's would on a
+    bf16 model, and the forwards take the native bf16 conv.  lin / lin+ have no bf16 kernels: their
+    rows are left out there (logged)."""
+    bf16 = dtype == torch.bfloat16
+    quantizers = {k: q for k, q in quantizer_dict.items() if not (bf16 and k in ("lin", "lin+"))}
+    if bf16:
+        log("dtype bf16: lin / lin+ rows left out (no bf16 lin quantizer)")
     rows: List[Row] = []
     model = get_model(model_type=model_type, num_classes=num_classes, quantize_fn=None, bits=4,
                       image_size=image_size)
     model.to(device)
     load_distributed_state_dict(model, os.path.join(seed_dir, "model_state", "full_precision.pth"))
-    acc = test_model(model, test_loader, device)
+    model.to(dtype)
+    acc = test_model(model, test_loader, device, dtype)
     log(f"full_precision = {acc * 100:.2f}%, q_error = 0.0")
     rows.append(("full_precision", acc, 0.0))
-    for quant_type, quantizer in quantizer_dict.items():  # post-training quantization
+    for quant_type, quantizer in quantizers.items():  # post-training quantization
         for b in bits:
             model_copy = deepcopy(model)
             quant_error = quantize_model(model=model_copy, quantizer=quantizer, bits=b)
-            acc = test_model(model_copy, test_loader, device)
+            acc = test_model(model_copy, test_loader, device, dtype)
             rows.append((f"ptq_{quant_type}_{b}", acc, quant_error))
             log(f"ptq_{quant_type}_{b} = {acc * 100:.2f}%, q_error = {quant_error:.10f}")
     if not skip_qat:  # quantization-aware-trained checkpoints
-        for quant_type, quantizer in quantizer_dict.items():
+        for quant_type, quantizer in quantizers.items():
             for b in bits:
                 cfg = f"{quant_type}_{b}"
                 m = get_model(model_type=model_type, num_classes=num_classes, quantize_fn=quantizer, bits=b,
                               image_size=image_size)
                 m.to(device)
                 load_distributed_state_dict(m, os.path.join(seed_dir, "model_state", f"{cfg}.pth"))
-                acc = test_model(m, test_loader, device)
+                m.to(dtype)
+                acc = test_model(m, test_loader, device, dtype)
                 quant_error = _qat_error(os.path.join(seed_dir, f"{cfg}.csv"))
                 rows.append((f"qat_{cfg}", acc, quant_error))
                 log(f"qat_{cfg} = {acc * 100:.2f}%, q_error = {quant_error:.10f}")
@@ -130,8 +144,9 @@ def tensor_loader(data_file: str, batch_size: int):
 
 
 def main(model_type: str, dataset: str, data_file: str, batch_size: int = 128, train_dir: str = "./train",
-         results_dir: str = "./results", skip_qat: bool = False) -> None:
+         results_dir: str = "./results", skip_qat: bool = False, dtype: str = "fp32") -> None:
     """test.py:58-164 with the evaluation set from data_file."""
+    assert dtype in DTYPES, "invalid dtype"
     assert torch.cuda.is_available(), "invalid hardware"
     assert model_type in ["resnet20", "resnet32", "resnet44", "resnet56", "mobilenet", "mobilevit"], \
         "invalid model type"
@@ -146,11 +161,12 @@ def main(model_type: str, dataset: str, data_file: str, batch_size: int = 128, t
     Path(results_work_dir).mkdir(parents=True, exist_ok=True)
     for seed_dir in sorted(glob.glob(f"{work_dir}/*")):
         seed = os.path.basename(seed_dir)
-        rows = evaluate_seed(model_type, num_classes, image_size, seed_dir, loader, device, skip_qat)
+        rows = evaluate_seed(model_type, num_classes, image_size, seed_dir, loader, device, skip_qat,
+                             dtype=DTYPES[dtype])
         write_results(f"{results_work_dir}/{seed}.csv", rows)
 
 
-if __name__ == "__main__":
+def arg_parser():
     import argparse
 
     ap = argparse.ArgumentParser(description=main.__doc__)
@@ -161,5 +177,11 @@ if __name__ == "__main__":
     ap.add_argument("--train_dir", default="./train")
     ap.add_argument("--results_dir", default="./results")
     ap.add_argument("--skip_qat", action="store_true")
-    a = ap.parse_args()
-    main(a.model_type, a.dataset, a.data_file, a.batch_size, a.train_dir, a.results_dir, a.skip_qat)
+    ap.add_argument("--dtype", choices=sorted(DTYPES), default="fp32",
+                    help="evaluate the models and their inputs in this dtype (bf16: model.bfloat16())")
+    return ap
+
+
+if __name__ == "__main__":
+    a = arg_parser().parse_args()
+    main(a.model_type, a.dataset, a.data_file, a.batch_size, a.train_dir, a.results_dir, a.skip_qat, a.dtype)
