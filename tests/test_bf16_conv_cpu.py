@@ -8,6 +8,7 @@ import torch
 from po2_quantization_amd import _lib, ptq
 from po2_quantization_amd.models.quantized_conv import QuantizedConv2d
 from po2_quantization_amd.utils.quantizers import quantizer_dict
+from tests import _bf16_cases as cases
 
 GEOM = dict(N=2, C=16, H=10, W=10, K=16, R=3, S=3, sh=1, sw=1, ph=1, pw=1, dh=1, dw=1, g=1)
 ORDER = ("N", "C", "H", "W", "K", "R", "S", "sh", "sw", "ph", "pw", "dh", "dw", "g")
@@ -97,3 +98,60 @@ def test_ptq_dtype_option():
     with pytest.raises(SystemExit):
         ap.parse_args(base + ["--dtype", "fp16"])
     assert ptq.DTYPES["bf16"] == torch.bfloat16
+
+
+# ---- coverage of the bf16 kernel family by the shared case table (tests/_bf16_cases.py) --------
+# Set-level conditions, not per-shape equalities: a planner retune fails these only when an
+# instance or a path is no longer reached by any shape tests/test_gpu_bf16_conv_paths.py runs.
+def _plans():
+    return [(s, cases.parse_plan(d), cases.parse_lds(d)) for s, d in ((s, cases.describe(s)) for s in cases.DENSE)]
+
+
+def test_case_table_reaches_every_instance():
+    reached = {(p.CC, p.NT, p.NJ) for _, p, _ in _plans()}
+    every = {(cc, nt, nj) for cc in (16, 32) for nt in (1, 2, 4) for nj in (1, 2, 4)}
+    missing = sorted(every - reached)
+    print("instances reached: %d of %d" % (len(reached & every), len(every)))
+    assert not missing, "no dense case reaches conv_bf16x1<CC, NT, NJ> for %s" % missing
+    assert reached == every, "instances outside the template grid: %s" % sorted(reached - every)
+
+
+CONDITIONS = {  # name -> predicate of (shape, plan, LDS bytes)
+    "kblocks > 1 together with chunks > 1": lambda s, p, lds: p.kblocks > 1 and p.chunks > 1,
+    "TQ % 4 != 0 (2-byte epilogue only)": lambda s, p, lds: p.TQ % 4 != 0,
+    "ksteps >= 13 with K > 16 and NT = 1 (NT halved to fit LDS)":
+        lambda s, p, lds: p.ksteps >= 13 and s[4] > 16 and p.NT == 1,
+    "tilesP > 1 and tilesQ > 1 with W even (pair staging)":
+        lambda s, p, lds: p.tilesP > 1 and p.tilesQ > 1 and s[3] % 2 == 0,
+    "tilesP > 1 and tilesQ > 1 with W odd (2-byte staging)":
+        lambda s, p, lds: p.tilesP > 1 and p.tilesQ > 1 and s[3] % 2 == 1,
+    "lds > 48 KiB": lambda s, p, lds: lds > 48 * 1024,
+}
+
+
+def test_case_table_meets_every_named_condition():
+    plans = _plans()
+    unmet = [name for name, cond in CONDITIONS.items() if not any(cond(s, p, lds) for s, p, lds in plans)]
+    for name, cond in CONDITIONS.items():
+        print("%s: %s" % (name, [cases.case_id(s) for s, p, lds in plans if cond(s, p, lds)]))
+    assert not unmet, "no dense case meets: %s" % unmet
+
+
+def test_alignment_cases_cover_both_stagings_and_both_stores():
+    seen = {(s[3] % 2 == 0, cases.parse_plan(cases.describe(s)).TQ % 4 == 0) for s in cases.ALIGNMENT}
+    missing = {(pair, vec) for pair in (True, False) for vec in (True, False)} - seen
+    assert not missing, "no alignment case has (pair staging, 8-byte stores) = %s" % sorted(missing)
+
+
+def test_depthwise_cases_run_the_depthwise_kernel():
+    for s in cases.DEPTHWISE:
+        assert cases.describe(s, groups=s[1]).startswith("kind=dw_bf16 "), s
+
+
+def test_too_large_kernel_is_refused_on_the_host():
+    with pytest.raises(_lib.Po2qError, match="LDS"):
+        cases.describe(cases.TOO_LARGE)
+    L = _lib.load()
+    for mode in (0, 1, 2):
+        assert L.po2q_qconv2d_bf16_workspace_bytes(*cases.geom14(cases.TOO_LARGE), 4, 1, mode) == 0
+    assert cases.describe(cases.LARGEST).startswith("kind=bf16x1 ")  # 9x9 is the largest that fits

@@ -13,7 +13,10 @@ reference's own bf16 arithmetic on CPU.
 
 Bit-exact cases use operands whose partial sums are exact in fp32 in any order (integer x in
 [-4, 4]; weights that are multiples of 2^-7 with scale 1, or j/8), so y must equal ref.to(bf16):
-this catches a wrong tap, a straddled row end or a wrong rounding."""
+this catches a wrong tap, a straddled row end or a wrong rounding.
+
+The operands, the reference and the bar live in tests/_bf16_cases.py, shared with
+tests/test_gpu_bf16_conv_paths.py (every kernel instance, staging and store path)."""
 import ctypes
 
 import pytest
@@ -25,11 +28,10 @@ from po2_quantization_amd import _lib
 from po2_quantization_amd.models.model import get_model
 from po2_quantization_amd.models.quantized_conv import QuantizedConv2d, _torch_epilogue
 from po2_quantization_amd.utils.quantizers import NATIVE_MODES, quantizer_dict
+from tests._bf16_cases import BF, BITS, MODES, assert_bar, exact_case, quantized, random_case, reference
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-BF = torch.bfloat16
-BITS = 4
 
 # (N, C, H, W, K, R, stride, pad, dil)
 SHAPES = [
@@ -47,50 +49,6 @@ SHAPES = [
 ]
 # depthwise (N, C, H, W, R, stride, pad), groups = C
 DW_SHAPES = [(2, 24, 9, 9, 3, 1, 1), (1, 40, 10, 7, 3, 2, 1), (1, 8, 6, 6, 5, 1, 2)]
-MODES = ["po2", "po2+", "none"]
-
-
-def quantized(w, mode):
-    return w if mode == "none" else _lib.restated_quantize(w, BITS, mode)
-
-
-def reference(x, q, b, stride, pad, dil, groups):
-    """(ref, mag) in fp64 on the CPU."""
-    bd = b.double() if b is not None else None
-    ref = F.conv2d(x.double(), q.double(), bd, stride, pad, dil, groups)
-    mag = F.conv2d(x.double().abs(), q.double().abs(), bd.abs() if bd is not None else None, stride, pad, dil, groups)
-    return ref, mag
-
-
-def assert_bar(y, ref, mag, k, what=""):
-    tol = 2.0 ** -8 * ref.abs() + (1 + 2.0 ** -8) * (k + 3) * 2.0 ** -23 * mag
-    err = (y.double().cpu() - ref).abs()
-    ratio = (err / tol.clamp_min(1e-300)).max().item()
-    print("%s worst |y - ref| / bar = %.3f" % (what, ratio))
-    assert torch.isfinite(y.float()).all(), what
-    assert bool((err <= tol).all()), (what, ratio)
-
-
-def random_case(shape, groups, seed, bias):
-    N, C, H, W, K, R = shape[:6]
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(N, C, H, W, generator=g).to(BF)
-    w = (torch.randn(K, C // groups, R, R, generator=g) * 0.1).to(BF)
-    b = torch.randn(K, generator=g).to(BF) if bias else None
-    return x, w, b
-
-
-def exact_case(shape, groups, seed, bias, mode):
-    N, C, H, W, K, R = shape[:6]
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randint(-4, 5, (N, C, H, W), generator=g).to(BF)
-    if mode == "none":
-        w = (torch.randint(-8, 9, (K, C // groups, R, R), generator=g).float() / 8).to(BF)
-    else:  # one element 1.0, the rest in [-1, 1]: the scale is 1 and Q(w) a multiple of 2^-7
-        w = (torch.rand(K, C // groups, R, R, generator=g) * 2 - 1).to(BF)
-        w.view(-1)[0] = 1.0
-    b = (torch.randint(-8, 9, (K,), generator=g).float() / 8).to(BF) if bias else None
-    return x, w, b
 
 
 def native(x, w, b, stride, pad, dil, groups, mode):
