@@ -201,6 +201,38 @@ int po2q_qconv2d_fused_f32(const float* x, const float* w, const float* bias, fl
                            void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * po2q_qconv2d_bf16 with the same eval-mode epilogue in the conv kernel's store: one launch for
+ * act(bn(conv(x)) + residual) of a model in bf16.  x, w, bias, y as for po2q_qconv2d_bf16;
+ * post_scale / post_shift are fp32 [K] (the eval BatchNorm folded by the caller, as for
+ * po2q_qconv2d_fused_f32); residual is bf16 [N, K, P, Q], laid out like y, and must not alias y
+ * or x.  Each of the three may be NULL.  act: enum po2q_act; any other value is PO2Q_ERR_INVALID.
+ * Arithmetic (the contract): per output, with acc the kernel's fp32 accumulator exactly as
+ * po2q_qconv2d_bf16 computes it,
+ *   v = acc + float(bias[k])                  (bias NULL: acc)
+ *   v = v * post_scale[k] + post_shift[k]     (fp32; NULL scale = 1, NULL shift = 0; skipped when
+ *                                              both are NULL; FMA contraction unspecified)
+ *   v = v + float(residual[n, k, p, q])       (skipped when NULL)
+ *   v = act(v)                                (fp32 relu / relu6 / silu of po2q_qconv2d_fused_f32,
+ *                                              NaN propagating)
+ *   y = bf16_rne(v)
+ * There is one rounding to bf16, at the end.  The module sequence of a bf16 model rounds to bf16
+ * after the conv, after the BatchNorm and after the add, so this result differs from it and is
+ * closer to the exact one.  With the three pointers NULL and PO2Q_ACT_NONE the entry returns the
+ * bits of po2q_qconv2d_bf16.
+ * Modes, groups and limits are those of po2q_qconv2d_bf16; the workspace is what
+ * po2q_qconv2d_bf16_workspace_bytes returns.  Every error returns before any launch and leaves y
+ * untouched.  Asynchronous, allocates nothing, safe under graph capture.
+ */
+int po2q_qconv2d_fused_bf16(const uint16_t* x, const uint16_t* w, const uint16_t* bias, uint16_t* y,
+                            int64_t N, int64_t C, int64_t H, int64_t W,
+                            int64_t K, int64_t R, int64_t S,
+                            int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
+                            int64_t dil_h, int64_t dil_w, int64_t groups,
+                            int bits, int fsr, int mode,
+                            const float* post_scale, const float* post_shift, const uint16_t* residual, int act,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Kernel autotuning, the counterpart of the reference's
  * torch.backends.cudnn.benchmark = True (train.py:33, test.py:31): times every
  * candidate plan for this problem on these buffers (synchronises the stream;

@@ -9,7 +9,7 @@ planning / tuning / diagnostic entry points, the two-enqueue SplitConv, and ever
 PO2Q_LIB points at another build of libpo2q.so (diagnostic builds).
 
 fp32 HIP tensors always run the native kernels: a missing library raises, there is no
-torch fallback for them.  bf16 HIP tensors have the forward-only qconv2d_bf16 (po2q_qconv2d_bf16).  The PO2 / PO2+ quantizer also takes fp64 and bf16 HIP tensors natively
+torch fallback for them.  bf16 HIP tensors have the forward-only qconv2d_bf16 (po2q_qconv2d_bf16) and qconv2d_fused_bf16 (po2q_qconv2d_fused_bf16).  The PO2 / PO2+ quantizer also takes fp64 and bf16 HIP tensors natively
 (the reference preserves dtype); other inputs (CPU tensors, fp16, ...) take
 restated_quantize, the reference formula written as torch ops in the input's dtype and device.
 """
@@ -71,6 +71,7 @@ EXPORTS = (
     "po2q_qconv2d_ir_f32",
     "po2q_qconv2d_bf16_workspace_bytes",
     "po2q_qconv2d_bf16",
+    "po2q_qconv2d_fused_bf16",
     "po2q_qconv2d_bf16_describe",
 )
 
@@ -195,6 +196,8 @@ def load():
     L.po2q_qconv2d_bf16_workspace_bytes.argtypes = [i64] * 14 + [i32, i32, i32]
     L.po2q_qconv2d_bf16.restype = i32
     L.po2q_qconv2d_bf16.argtypes = [p, p, p, p] + [i64] * 14 + [i32, i32, i32, p, sz, p]
+    L.po2q_qconv2d_fused_bf16.restype = i32
+    L.po2q_qconv2d_fused_bf16.argtypes = [p, p, p, p] + [i64] * 14 + [i32, i32, i32, p, p, p, i32, p, sz, p]
     L.po2q_qconv2d_bf16_describe.restype = i32
     L.po2q_qconv2d_bf16_describe.argtypes = [i64] * 14 + [i32, i32, i32, ctypes.c_char_p, sz]
     _lib = L
@@ -408,11 +411,8 @@ def _require_hip_bf16(t, what):
                         % (what, t.dtype))
 
 
-def qconv2d_bf16(x, w, bias=None, stride=1, padding=0, dilation=1, groups=1, bits=4, mode="po2", fsr=1):
-    """The reference's forward with every tensor bf16 (model.bfloat16(): F.conv2d(x, Q(w), bias, ...) on
-    bf16 tensors, models/quantized_conv.py:32-38) as one native call (po2q_qconv2d_bf16): Q(w) exactly
-    quantize(w) in bf16, one bf16 MFMA pass with fp32 accumulation, bf16 out.  mode "none" / "po2" /
-    "po2+"; groups 1 or depthwise.  Forward only."""
+def _bf16_geometry(x, w, bias, stride, padding, dilation, groups):
+    """The checks of the bf16 conv entries; returns the 14 geometry arguments and y's shape."""
     _require_hip_bf16(x, "input")
     _require_hip_bf16(w, "weight")
     if bias is not None:
@@ -429,17 +429,25 @@ def qconv2d_bf16(x, w, bias=None, stride=1, padding=0, dilation=1, groups=1, bit
     sh, sw = _pair(stride)
     ph, pw = _pair(padding)
     dh, dw = _pair(dilation)
-    mode_id = MODES[mode]
     args = (N, C, H, W, K, R, S, sh, sw, ph, pw, dh, dw, int(groups))
     P = (H + 2 * ph - dh * (R - 1) - 1) // sh + 1 if sh > 0 else 0
     Q = (W + 2 * pw - dw * (S - 1) - 1) // sw + 1 if sw > 0 else 0
-    yshape = (N, K, max(P, 0), max(Q, 0))
-    if N == 0:  # an empty batch: torch's F.conv2d returns an empty output
+    return args, (N, K, max(P, 0), max(Q, 0))
+
+
+def qconv2d_bf16(x, w, bias=None, stride=1, padding=0, dilation=1, groups=1, bits=4, mode="po2", fsr=1):
+    """The reference's forward with every tensor bf16 (model.bfloat16(): F.conv2d(x, Q(w), bias, ...) on
+    bf16 tensors, models/quantized_conv.py:32-38) as one native call (po2q_qconv2d_bf16): Q(w) exactly
+    quantize(w) in bf16, one bf16 MFMA pass with fp32 accumulation, bf16 out.  mode "none" / "po2" /
+    "po2+"; groups 1 or depthwise.  Forward only."""
+    args, yshape = _bf16_geometry(x, w, bias, stride, padding, dilation, groups)
+    mode_id = MODES[mode]
+    if yshape[0] == 0:  # an empty batch: torch's F.conv2d returns an empty output
         return torch.empty(yshape, dtype=torch.bfloat16, device=x.device)
     O = ops()
     if O is not None:
-        return _op_call(O.qconv2d_bf16, x, w, bias, [sh, sw], [ph, pw], [dh, dw], int(groups), int(bits), mode_id,
-                        int(fsr))
+        return _op_call(O.qconv2d_bf16, x, w, bias, list(args[7:9]), list(args[9:11]), list(args[11:13]), args[13],
+                        int(bits), mode_id, int(fsr))
     L = load()
     xc, wc = x.contiguous(), w.contiguous()
     bc = bias.contiguous() if bias is not None else None
@@ -452,6 +460,56 @@ def qconv2d_bf16(x, w, bias=None, stride=1, padding=0, dilation=1, groups=1, bit
         _check(L.po2q_qconv2d_bf16(xc.data_ptr(), wc.data_ptr(), bc.data_ptr() if bc is not None else None,
                                    y.data_ptr(), *args, int(bits), int(fsr), mode_id, ws.data_ptr(), ws.numel(),
                                    _stream(xc.device)))
+    return y
+
+
+def qconv2d_fused_bf16(x, w, bias=None, stride=1, padding=0, dilation=1, groups=1, bits=4, mode="po2", fsr=1,
+                       post_scale=None, post_shift=None, residual=None, act="none"):
+    """qconv2d_bf16 with the eval epilogue in the conv kernel's store (po2q_qconv2d_fused_bf16):
+        y = bf16(act((acc + bias) * post_scale[k] + post_shift[k] + residual))
+    on the kernel's fp32 accumulator, one rounding to bf16 at the end.  post_scale / post_shift: fp32 [K]
+    (an eval BatchNorm folded in fp32 by the caller) or None; residual: a bf16 tensor of y's shape or
+    None (it may not alias x); act: "none" | "relu" | "relu6" | "silu".  Forward only."""
+    args, yshape = _bf16_geometry(x, w, bias, stride, padding, dilation, groups)
+    mode_id = MODES[mode]
+    ext = []
+    for t, what in ((post_scale, "post_scale"), (post_shift, "post_shift")):
+        if t is not None:
+            _require_hip_f32(t, what)
+            if t.device != x.device:
+                raise Po2qError("po2q: %s must be on the input's device" % what)
+            if t.numel() != yshape[1]:
+                raise Po2qError("po2q: %s must have %d elements, got %d" % (what, yshape[1], t.numel()))
+            t = t.contiguous()
+        ext.append(t)
+    rc = None
+    if residual is not None:
+        _require_hip_bf16(residual, "residual")
+        if residual.device != x.device:
+            raise Po2qError("po2q: residual must be on the input's device")
+        if tuple(residual.shape) != tuple(yshape):
+            raise Po2qError("po2q: residual shape %s does not match the output %s"
+                            % (list(residual.shape), list(yshape)))
+        rc = residual.contiguous()
+    if yshape[0] == 0:
+        return torch.empty(yshape, dtype=torch.bfloat16, device=x.device)
+    O = ops()
+    if O is not None:
+        return _op_call(O.qconv2d_fused_bf16, x, w, bias, list(args[7:9]), list(args[9:11]), list(args[11:13]),
+                        args[13], int(bits), mode_id, int(fsr), ext[0], ext[1], rc, ACTS[act])
+    L = load()
+    xc, wc = x.contiguous(), w.contiguous()
+    bc = bias.contiguous() if bias is not None else None
+    with torch.cuda.device(xc.device):
+        nbytes = L.po2q_qconv2d_bf16_workspace_bytes(*args, int(bits), int(fsr), mode_id)
+        if nbytes == 0:
+            _check(1)
+        y = torch.empty(yshape, dtype=torch.bfloat16, device=xc.device)
+        ws = _workspace(nbytes, xc.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        _check(L.po2q_qconv2d_fused_bf16(xc.data_ptr(), wc.data_ptr(), ptr(bc), y.data_ptr(), *args, int(bits),
+                                         int(fsr), mode_id, ptr(ext[0]), ptr(ext[1]), ptr(rc), ACTS[act],
+                                         ws.data_ptr(), ws.numel(), _stream(xc.device)))
     return y
 
 

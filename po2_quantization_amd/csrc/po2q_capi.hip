@@ -635,13 +635,18 @@ size_t po2q_qconv2d_bf16_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_
     return b16_workspace_bytes(p);
 }
 
-int po2q_qconv2d_bf16(const uint16_t* x, const uint16_t* w, const uint16_t* bias, uint16_t* y, int64_t N, int64_t C,
-                      int64_t H, int64_t W, int64_t K, int64_t R, int64_t S, int64_t stride_h, int64_t stride_w,
-                      int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t groups, int bits, int fsr,
-                      int mode, void* workspace, size_t workspace_bytes, void* stream) {
+// po2q_qconv2d_bf16 (an empty epilogue) and po2q_qconv2d_fused_bf16: every check, then b16_run
+static int b16_conv(const uint16_t* x, const uint16_t* w, const uint16_t* bias, uint16_t* y, int64_t N, int64_t C,
+                    int64_t H, int64_t W, int64_t K, int64_t R, int64_t S, int64_t stride_h, int64_t stride_w,
+                    int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t groups, int bits, int fsr,
+                    int mode, const B16Epi& e, void* workspace, size_t workspace_bytes, void* stream) {
     if (!check_mode_bits(mode, bits, true)) return PO2Q_ERR_INVALID;
     if (!x || !w || !y || !workspace) {
         set_error("po2q: null pointer");
+        return PO2Q_ERR_INVALID;
+    }
+    if (e.act < PO2Q_ACT_NONE || e.act > PO2Q_ACT_SILU) {
+        set_error("po2q: unknown activation " + std::to_string(e.act));
         return PO2Q_ERR_INVALID;
     }
     ConvPlan p;
@@ -653,8 +658,28 @@ int po2q_qconv2d_bf16(const uint16_t* x, const uint16_t* w, const uint16_t* bias
         set_error("po2q: conv workspace too small (need " + std::to_string(need) + " bytes)");
         return PO2Q_ERR_WORKSPACE;
     }
-    return hip_status(b16_run(p, x, w, bias, y, bits, fsr, mode, workspace, reinterpret_cast<hipStream_t>(stream)),
+    return hip_status(b16_run(p, x, w, bias, y, bits, fsr, mode, workspace, reinterpret_cast<hipStream_t>(stream), e),
                       "bf16 conv launch");
+}
+
+int po2q_qconv2d_bf16(const uint16_t* x, const uint16_t* w, const uint16_t* bias, uint16_t* y, int64_t N, int64_t C,
+                      int64_t H, int64_t W, int64_t K, int64_t R, int64_t S, int64_t stride_h, int64_t stride_w,
+                      int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t groups, int bits, int fsr,
+                      int mode, void* workspace, size_t workspace_bytes, void* stream) {
+    return b16_conv(x, w, bias, y, N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, bits,
+                    fsr, mode, B16Epi{}, workspace, workspace_bytes, stream);
+}
+
+int po2q_qconv2d_fused_bf16(const uint16_t* x, const uint16_t* w, const uint16_t* bias, uint16_t* y, int64_t N,
+                            int64_t C, int64_t H, int64_t W, int64_t K, int64_t R, int64_t S, int64_t stride_h,
+                            int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w,
+                            int64_t groups, int bits, int fsr, int mode, const float* post_scale,
+                            const float* post_shift, const uint16_t* residual, int act, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    B16Epi e;
+    e.ps = post_scale; e.pb = post_shift; e.res = residual; e.act = act;
+    return b16_conv(x, w, bias, y, N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, bits,
+                    fsr, mode, e, workspace, workspace_bytes, stream);
 }
 
 int po2q_qconv2d_bf16_describe(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t R, int64_t S,

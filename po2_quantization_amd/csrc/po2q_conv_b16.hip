@@ -27,6 +27,16 @@
 //   inside the row or outside it as a whole.  Every other shape stages with 2-byte loads.
 // groups == C == K, R, S <= 5: conv_dw_b16, one output per thread, fp32 FMAs in tap order, padded
 //   taps skipped.
+//
+// Fused epilogue (po2q_qconv2d_fused_bf16): both kernels carry a template flag EPI.  The EPI = false
+// instances are the kernels above, unchanged; the EPI = true instances apply, on the fp32
+// accumulator and before the single rounding to bf16,
+//   v = acc + bias[k];  v = v * ps[k] + pb[k];  v += residual[n, k, p, q];  y = bf16_rne(act(v)).
+// ps / pb are loaded once per (nt, lane & 15) beside the bias.  The residual is read with the y
+// store's own index arithmetic: one 8-byte load where the lane's 4 pixels go out as one 8-byte
+// store and the residual address is 8-byte aligned too (tested per lane), else 2-byte loads under
+// the guard of the 2-byte stores, so no element outside [N, K, P, Q] is read.  The activation is
+// dispatched once per block (with_act).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,6 +44,7 @@
 #include <cstdio>
 #include <vector>
 
+#include "po2q_epi.h"
 #include "po2q_internal.h"
 #include "po2q_quant_b16_dev.h"
 #include "po2q_x3_dev.h"
@@ -54,11 +65,24 @@ struct B16Args {
 // (a & 0xffff) | (b << 16): the low bf16 halves of a (low) and b (high) as one dword
 __device__ __forceinline__ uint32_t pk_lo16(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); }
 
-template <int CC, int NT, int NJ>
-__global__ __launch_bounds__(kThreads) void conv_bf16x1(const uint16_t* __restrict__ x,
+// The fused epilogue on a lane's 4 values: v * sk + tk (when aff), + residual (when has), activation
+template <int ACT>
+__device__ __forceinline__ void b16_epi4(float (&v)[4], bool aff, float sk, float tk, bool has,
+                                         const float (&rv)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (aff) v[i] = v[i] * sk + tk;
+        if (has) v[i] += rv[i];
+        v[i] = epi_act_ct<ACT>(v[i]);
+    }
+}
+
+// (the largest fused instance is held to the 3 waves per SIMD its plain twin runs at)
+template <int CC, int NT, int NJ, bool EPI>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(EPI && NT * NJ == 16 ? 3 : 1))) void conv_bf16x1(const uint16_t* __restrict__ x,
                                                         const uint4* __restrict__ wpk,
                                                         const uint16_t* __restrict__ bias,
-                                                        uint16_t* __restrict__ y, B16Args a) {
+                                                        uint16_t* __restrict__ y, B16Args a, B16Epi e) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int OCT = CC / 8;  // channel octets per tap
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -173,34 +197,134 @@ __global__ __launch_bounds__(kThreads) void conv_bf16x1(const uint16_t* __restri
 
     // ---- epilogue: D[row = pixel 4*(lane>>4)+i][col = channel lane&15]
     const int64_t PQ = (int64_t)a.P * a.Q;
+    if constexpr (!EPI) {
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int k = kb * 16 * NT + nt * 16 + (lane & 15);
-        if (k >= a.K) continue;  // channels past K are not stored
-        const float bk = bias ? bf16_to_f(bias[k]) : 0.0f;
-        uint16_t* yk = y + ((int64_t)n * a.K + k) * PQ;
+        for (int nt = 0; nt < NT; ++nt) {
+            const int k = kb * 16 * NT + nt * 16 + (lane & 15);
+            if (k >= a.K) continue;  // channels past K are not stored
+            const float bk = bias ? bf16_to_f(bias[k]) : 0.0f;
+            uint16_t* yk = y + ((int64_t)n * a.K + k) * PQ;
 #pragma unroll
-        for (int g = 0; g < NJ; ++g) {
-            const int i0 = (wave * NJ + g) * 16 + 4 * o;
-            if (i0 >= npix) continue;
-            uint32_t r[4];
+            for (int g = 0; g < NJ; ++g) {
+                const int i0 = (wave * NJ + g) * 16 + 4 * o;
+                if (i0 >= npix) continue;
+                uint32_t r[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) r[i] = bf16_rne(acc[g][nt][i] + bk);
-            const int pl = i0 / a.TQ, ql = i0 - pl * a.TQ;
-            const int pp = p0 + pl, qq = q0 + ql;
-            uint16_t* yp = yk + (int64_t)pp * a.Q + qq;
-            if (a.vec && pp < a.P && qq + 3 < a.Q && (reinterpret_cast<uintptr_t>(yp) & 7u) == 0) {
-                *reinterpret_cast<uint2*>(yp) = make_uint2(r[0] | (r[1] << 16), r[2] | (r[3] << 16));
-            } else {
+                for (int i = 0; i < 4; ++i) r[i] = bf16_rne(acc[g][nt][i] + bk);
+                const int pl = i0 / a.TQ, ql = i0 - pl * a.TQ;
+                const int pp = p0 + pl, qq = q0 + ql;
+                uint16_t* yp = yk + (int64_t)pp * a.Q + qq;
+                if (a.vec && pp < a.P && qq + 3 < a.Q && (reinterpret_cast<uintptr_t>(yp) & 7u) == 0) {
+                    *reinterpret_cast<uint2*>(yp) = make_uint2(r[0] | (r[1] << 16), r[2] | (r[3] << 16));
+                } else {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int idx = i0 + i;
-                    const int pli = idx / a.TQ, qli = idx - pli * a.TQ;
-                    const int ppi = p0 + pli, qqi = q0 + qli;
-                    if (idx < npix && ppi < a.P && qqi < a.Q) yk[(int64_t)ppi * a.Q + qqi] = (uint16_t)r[i];
+                    for (int i = 0; i < 4; ++i) {
+                        const int idx = i0 + i;
+                        const int pli = idx / a.TQ, qli = idx - pli * a.TQ;
+                        const int ppi = p0 + pli, qqi = q0 + qli;
+                        if (idx < npix && ppi < a.P && qqi < a.Q) yk[(int64_t)ppi * a.Q + qqi] = (uint16_t)r[i];
+                    }
                 }
             }
         }
+    } else {
+        // the same stores with the fused epilogue in front of the one rounding; the activation is
+        // dispatched once per block (with_act), never per value.
+        // Loads are kept apart from the stores.  On gfx9 one counter (vmcnt) covers loads and stores, and
+        // behind the divergent store branches the compiler can only wait for all of them: a load between
+        // two stores would drain the stores first.  So the per-channel bias / scale / shift of all NT
+        // tiles are loaded, and waited for, before the first store, and a tile's residual values for
+        // all its NJ pixel groups are requested together (packed, two bf16 per register) and waited for
+        // once: no wait is left between stores without a residual, one per tile with one.
+        constexpr int kWaitVm0 = 0x0F70;  // s_waitcnt vmcnt(0) alone (expcnt 7, lgkmcnt 15: not waited)
+        const bool aff = e.ps || e.pb;
+        float bk[NT], sk[NT], tk[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int k = min(kb * 16 * NT + nt * 16 + (lane & 15), a.K - 1);  // lanes past K load, never store
+            bk[nt] = bias ? bf16_to_f(bias[k]) : 0.0f;
+            sk[nt] = e.ps ? e.ps[k] : 1.0f;
+            tk[nt] = e.pb ? e.pb[k] : 0.0f;
+        }
+        __builtin_amdgcn_s_waitcnt(kWaitVm0);
+        with_act(e.act, [&](auto act_c) {
+            constexpr int ACT = decltype(act_c)::value;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const int k = kb * 16 * NT + nt * 16 + (lane & 15);
+                if (k >= a.K) continue;  // channels past K are not stored
+                const uint16_t* rk = e.res ? e.res + ((int64_t)n * a.K + k) * PQ : nullptr;
+                uint16_t* yk = y + ((int64_t)n * a.K + k) * PQ;
+                // (the 8-byte load and the packed 2-byte loads land in registers of their own, OR-ed after
+                // the wait: one register for both would make the compiler wait inside each branch)
+                uint2 rq[NJ];
+                uint32_t rp[NJ][2];
+                if (rk) {
+#pragma unroll
+                    for (int g = 0; g < NJ; ++g) {
+                        rp[g][0] = rp[g][1] = 0u;
+                        rq[g] = make_uint2(0u, 0u);
+                        const int i0 = (wave * NJ + g) * 16 + 4 * o;
+                        if (i0 >= npix) continue;
+                        const int pl = i0 / a.TQ, ql = i0 - pl * a.TQ;
+                        const int pp = p0 + pl, qq = q0 + ql;
+                        const int64_t off = (int64_t)pp * a.Q + qq;
+                        const bool vst =
+                            a.vec && pp < a.P && qq + 3 < a.Q && (reinterpret_cast<uintptr_t>(yk + off) & 7u) == 0;
+                        // the residual with the store's index arithmetic: 8 bytes at once only where y
+                        // goes out so and this lane's residual address is 8-byte aligned as well
+                        if (vst && (reinterpret_cast<uintptr_t>(rk + off) & 7u) == 0) {
+                            rq[g] = *reinterpret_cast<const uint2*>(rk + off);
+                        } else {
+                            uint32_t d[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) {
+                                const int idx = i0 + i;
+                                const int pli = idx / a.TQ, qli = idx - pli * a.TQ;
+                                const int ppi = p0 + pli, qqi = q0 + qli;
+                                if (idx < npix && ppi < a.P && qqi < a.Q) d[i] = rk[(int64_t)ppi * a.Q + qqi];
+                            }
+                            rp[g][0] = d[0] | (d[1] << 16);
+                            rp[g][1] = d[2] | (d[3] << 16);
+                        }
+                    }
+                    __builtin_amdgcn_s_waitcnt(kWaitVm0);
+                }
+#pragma unroll
+                for (int g = 0; g < NJ; ++g) {
+                    const int i0 = (wave * NJ + g) * 16 + 4 * o;
+                    if (i0 >= npix) continue;
+                    float v[4], rv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) v[i] = acc[g][nt][i] + bk[nt];
+                    if (rk) {
+                        const uint32_t d0 = rq[g].x | rp[g][0], d1 = rq[g].y | rp[g][1];
+                        rv[0] = __uint_as_float(d0 << 16);
+                        rv[1] = __uint_as_float(d0 & 0xffff0000u);
+                        rv[2] = __uint_as_float(d1 << 16);
+                        rv[3] = __uint_as_float(d1 & 0xffff0000u);
+                    }
+                    b16_epi4<ACT>(v, aff, sk[nt], tk[nt], rk != nullptr, rv);
+                    uint32_t r[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) r[i] = bf16_rne(v[i]);  // the one rounding
+                    const int pl = i0 / a.TQ, ql = i0 - pl * a.TQ;
+                    const int pp = p0 + pl, qq = q0 + ql;
+                    uint16_t* yp = yk + (int64_t)pp * a.Q + qq;
+                    if (a.vec && pp < a.P && qq + 3 < a.Q && (reinterpret_cast<uintptr_t>(yp) & 7u) == 0) {
+                        *reinterpret_cast<uint2*>(yp) = make_uint2(r[0] | (r[1] << 16), r[2] | (r[3] << 16));
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const int idx = i0 + i;
+                            const int pli = idx / a.TQ, qli = idx - pli * a.TQ;
+                            const int ppi = p0 + pli, qqi = q0 + qli;
+                            if (idx < npix && ppi < a.P && qqi < a.Q) yk[(int64_t)ppi * a.Q + qqi] = (uint16_t)r[i];
+                        }
+                    }
+                }
+            }
+        });
     }
 }
 
@@ -210,10 +334,10 @@ struct DwB16Args {
     int64_t total;  // N * C * P * Q
 };
 
-__global__ __launch_bounds__(kThreads) void conv_dw_b16(const uint16_t* __restrict__ x,
-                                                        const uint16_t* __restrict__ qw,
-                                                        const uint16_t* __restrict__ bias,
-                                                        uint16_t* __restrict__ y, DwB16Args a) {
+template <bool EPI, int ACT>
+__device__ __forceinline__ void dw_b16_body(const uint16_t* __restrict__ x, const uint16_t* __restrict__ qw,
+                                            const uint16_t* __restrict__ bias, uint16_t* __restrict__ y,
+                                            const DwB16Args& a, const B16Epi& e) {
     const int64_t stride = (int64_t)gridDim.x * kThreads;
     const int64_t PQ = (int64_t)a.P * a.Q, HW = (int64_t)a.H * a.W;
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < a.total; i += stride) {
@@ -233,8 +357,25 @@ __global__ __launch_bounds__(kThreads) void conv_dw_b16(const uint16_t* __restri
                 acc = fmaf(bf16_to_f(xc[(int64_t)h * a.W + w]), bf16_to_f(wc[r * a.S + s]), acc);
             }
         }
-        y[i] = bf16_rne(acc + (bias ? bf16_to_f(bias[c]) : 0.0f));
+        float v = acc + (bias ? bf16_to_f(bias[c]) : 0.0f);
+        if constexpr (EPI) {
+            if (e.ps || e.pb) v = v * (e.ps ? e.ps[c] : 1.0f) + (e.pb ? e.pb[c] : 0.0f);
+            if (e.res) v += bf16_to_f(e.res[i]);  // laid out like y: the store's own index
+            v = epi_act_ct<ACT>(v);
+        }
+        y[i] = bf16_rne(v);
     }
+}
+
+template <bool EPI>
+__global__ __launch_bounds__(kThreads) void conv_dw_b16(const uint16_t* __restrict__ x,
+                                                        const uint16_t* __restrict__ qw,
+                                                        const uint16_t* __restrict__ bias,
+                                                        uint16_t* __restrict__ y, DwB16Args a, B16Epi e) {
+    if constexpr (EPI)
+        with_act(e.act, [&](auto act_c) { dw_b16_body<true, decltype(act_c)::value>(x, qw, bias, y, a, e); });
+    else
+        dw_b16_body<false, 0>(x, qw, bias, y, a, e);
 }
 
 // ---- weight staging: max|w| partials, then quantize + pack ---------------------------------
@@ -318,30 +459,35 @@ int b16_parts(int64_t n) { return (int)std::min<int64_t>(kB16Parts, std::max<int
 
 template <int CC, int NT, int NJ>
 hipError_t launch_b16_t(const ConvPlan& p, const B16Args& a, const uint16_t* x, const uint16_t* packed,
-                        const uint16_t* bias, uint16_t* y, hipStream_t s) {
-    hipLaunchKernelGGL((conv_bf16x1<CC, NT, NJ>), dim3((unsigned)p.blocks), dim3(kThreads), p.lds_bytes, s, x,
-                       reinterpret_cast<const uint4*>(packed), bias, y, a);
+                        const uint16_t* bias, uint16_t* y, const B16Epi& e, hipStream_t s) {
+    // the plain entry (and a fused call with nothing to fuse) runs the EPI = false instance
+    if (e.any())
+        hipLaunchKernelGGL((conv_bf16x1<CC, NT, NJ, true>), dim3((unsigned)p.blocks), dim3(kThreads), p.lds_bytes, s,
+                           x, reinterpret_cast<const uint4*>(packed), bias, y, a, e);
+    else
+        hipLaunchKernelGGL((conv_bf16x1<CC, NT, NJ, false>), dim3((unsigned)p.blocks), dim3(kThreads), p.lds_bytes, s,
+                           x, reinterpret_cast<const uint4*>(packed), bias, y, a, e);
     return hipGetLastError();
 }
 
 template <int CC, int NT>
 hipError_t launch_b16_nj(const ConvPlan& p, const B16Args& a, const uint16_t* x, const uint16_t* packed,
-                         const uint16_t* bias, uint16_t* y, hipStream_t s) {
+                         const uint16_t* bias, uint16_t* y, const B16Epi& e, hipStream_t s) {
     switch (p.NJ) {
-        case 1: return launch_b16_t<CC, NT, 1>(p, a, x, packed, bias, y, s);
-        case 2: return launch_b16_t<CC, NT, 2>(p, a, x, packed, bias, y, s);
-        case 4: return launch_b16_t<CC, NT, 4>(p, a, x, packed, bias, y, s);
+        case 1: return launch_b16_t<CC, NT, 1>(p, a, x, packed, bias, y, e, s);
+        case 2: return launch_b16_t<CC, NT, 2>(p, a, x, packed, bias, y, e, s);
+        case 4: return launch_b16_t<CC, NT, 4>(p, a, x, packed, bias, y, e, s);
         default: return hipErrorInvalidValue;
     }
 }
 
 template <int CC>
 hipError_t launch_b16_nt(const ConvPlan& p, const B16Args& a, const uint16_t* x, const uint16_t* packed,
-                         const uint16_t* bias, uint16_t* y, hipStream_t s) {
+                         const uint16_t* bias, uint16_t* y, const B16Epi& e, hipStream_t s) {
     switch (p.NT) {
-        case 1: return launch_b16_nj<CC, 1>(p, a, x, packed, bias, y, s);
-        case 2: return launch_b16_nj<CC, 2>(p, a, x, packed, bias, y, s);
-        case 4: return launch_b16_nj<CC, 4>(p, a, x, packed, bias, y, s);
+        case 1: return launch_b16_nj<CC, 1>(p, a, x, packed, bias, y, e, s);
+        case 2: return launch_b16_nj<CC, 2>(p, a, x, packed, bias, y, e, s);
+        case 4: return launch_b16_nj<CC, 4>(p, a, x, packed, bias, y, e, s);
         default: return hipErrorInvalidValue;
     }
 }
@@ -450,7 +596,7 @@ void b16_describe(const ConvPlan& p, char* buf, size_t len) {
 }
 
 hipError_t b16_run(const ConvPlan& p, const uint16_t* x, const uint16_t* w, const uint16_t* bias, uint16_t* y, int bits,
-                   int fsr, int mode, void* workspace, hipStream_t s) {
+                   int fsr, int mode, void* workspace, hipStream_t s, const B16Epi& epi) {
     uint32_t* partial = reinterpret_cast<uint32_t*>(workspace);
     uint16_t* packed =
         reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(workspace) + align256((size_t)kB16Parts * sizeof(uint32_t)));
@@ -481,7 +627,12 @@ hipError_t b16_run(const ConvPlan& p, const uint16_t* x, const uint16_t* w, cons
         d.C = p.C; d.H = p.H; d.W = p.W; d.P = p.P; d.Q = p.Q; d.R = p.R; d.S = p.S;
         d.sh = p.sh; d.sw = p.sw; d.ph = p.ph; d.pw = p.pw; d.dh = p.dh; d.dw = p.dw;
         d.total = (int64_t)p.N * p.C * p.P * p.Q;
-        hipLaunchKernelGGL(conv_dw_b16, dim3((unsigned)p.blocks), dim3(kThreads), 0, s, x, packed, bias, y, d);
+        if (epi.any())
+            hipLaunchKernelGGL(conv_dw_b16<true>, dim3((unsigned)p.blocks), dim3(kThreads), 0, s, x, packed, bias, y, d,
+                               epi);
+        else
+            hipLaunchKernelGGL(conv_dw_b16<false>, dim3((unsigned)p.blocks), dim3(kThreads), 0, s, x, packed, bias, y,
+                               d, epi);
         return hipGetLastError();
     }
     B16Args a;
@@ -493,8 +644,8 @@ hipError_t b16_run(const ConvPlan& p, const uint16_t* x, const uint16_t* w, cons
     a.tap_off = a.w_off + p.steps * p.NT * 1024;
     a.pair = (p.W % 2 == 0 && (reinterpret_cast<uintptr_t>(x) & 3u) == 0) ? 1 : 0;
     a.vec = (p.TQ % 4 == 0) ? 1 : 0;
-    if (p.CC == 16) return launch_b16_nt<16>(p, a, x, packed, bias, y, s);
-    return launch_b16_nt<32>(p, a, x, packed, bias, y, s);
+    if (p.CC == 16) return launch_b16_nt<16>(p, a, x, packed, bias, y, epi, s);
+    return launch_b16_nt<32>(p, a, x, packed, bias, y, epi, s);
 }
 
 }  // namespace po2q

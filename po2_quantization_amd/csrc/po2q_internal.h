@@ -249,12 +249,20 @@ hipError_t launch_quantize_dt(const T* w, T* out, int64_t n, int bits, int fsr, 
 // bf16 conv (po2q_conv_b16.hip): x, w, bias, y as bf16 bit patterns.  b16_plan fills the tile of a
 // validated geometry (heuristic only; kind KIND_BF16X1 or KIND_DW_BF16) and returns 0 or the
 // PO2Q_ERR_* code with the error set; b16_run enqueues max|w| (quantized modes), the quantize +
-// pack and the conv.
+// pack and the conv.  With a B16Epi that has anything set (po2q_qconv2d_fused_bf16) the conv is the
+// EPI instance of the same kernel: y = bf16_rne(act((acc + bias) * ps[k] + pb[k] + res)).
+struct B16Epi {
+    const float* ps = nullptr;      // post_scale [K] or NULL
+    const float* pb = nullptr;      // post_shift [K] or NULL
+    const uint16_t* res = nullptr;  // residual [N, K, P, Q] bf16 or NULL
+    int act = 0;                    // PO2Q_ACT_*
+    bool any() const { return ps || pb || res || act != 0; }
+};
 int b16_plan(ConvPlan& p);
 size_t b16_workspace_bytes(const ConvPlan& p);
 void b16_describe(const ConvPlan& p, char* buf, size_t len);
 hipError_t b16_run(const ConvPlan& p, const uint16_t* x, const uint16_t* w, const uint16_t* bias, uint16_t* y,
-                   int bits, int fsr, int mode, void* workspace, hipStream_t s);
+                   int bits, int fsr, int mode, void* workspace, hipStream_t s, const B16Epi& e = B16Epi{});
 
 // lin / lin+ quantizer (po2q_lin.hip): w, out [d0, d1, rs = d2*d3], one block per d1 channel
 hipError_t launch_quantize_lin(const float* w, float* out, int d0, int d1, int rs, int bits, int num_iters, int plus,

@@ -27,6 +27,8 @@
 //                        packed workspaces (mobilenet.py:53-134, mobile_vit.py:131-239)
 //   po2q::qconv2d_bf16   QuantizedConv2d.forward of a model in bf16 (model.bfloat16()): every tensor
 //                        bf16, one bf16 MFMA pass (po2q_qconv2d_bf16); forward only
+//   po2q::qconv2d_fused_bf16  the same + eval BatchNorm affine (fp32), bf16 residual add and activation
+//                        in the conv kernel's store, one rounding to bf16 (po2q_qconv2d_fused_bf16)
 // Meta kernels give the output shapes (FX / torch.compile tracing, fake tensors).
 // Errors are TORCH_CHECK -> RuntimeError, as F.conv2d raises for bad arguments.
 #include <ATen/ATen.h>
@@ -255,9 +257,12 @@ std::vector<int64_t> conv_out_shape(const at::Tensor& x, const at::Tensor& w, at
     return {x.size(0), w.size(0), std::max<int64_t>(P, 0), std::max<int64_t>(Q, 0)};
 }
 
-at::Tensor qconv2d_bf16(const at::Tensor& x_, const at::Tensor& w_, const c10::optional<at::Tensor>& bias_,
-                        at::IntArrayRef stride, at::IntArrayRef padding, at::IntArrayRef dilation, int64_t groups,
-                        int64_t bits, int64_t mode, int64_t fsr) {
+// qconv2d_bf16 (fused false) and qconv2d_fused_bf16: the checks, the workspace and the one C ABI call
+at::Tensor qconv2d_bf16_impl(const at::Tensor& x_, const at::Tensor& w_, const c10::optional<at::Tensor>& bias_,
+                             at::IntArrayRef stride, at::IntArrayRef padding, at::IntArrayRef dilation, int64_t groups,
+                             int64_t bits, int64_t mode, int64_t fsr, bool fused,
+                             const c10::optional<at::Tensor>& post_scale_, const c10::optional<at::Tensor>& post_shift_,
+                             const c10::optional<at::Tensor>& residual_, int64_t act) {
     check_hip_bf16(x_, "input");
     check_hip_bf16(w_, "weight");
     const std::vector<int64_t> yshape = conv_out_shape(x_, w_, stride, padding, dilation);
@@ -273,6 +278,24 @@ at::Tensor qconv2d_bf16(const at::Tensor& x_, const at::Tensor& w_, const c10::o
     TORCH_CHECK(w_.size(1) * groups == x_.size(1), "po2q: Given groups=", groups, ", weight of size ", w_.sizes(),
                 ", expected input", x_.sizes(), " to have ", w_.size(1) * groups, " channels, but got ", x_.size(1),
                 " channels instead");
+    c10::optional<at::Tensor> ps, pb, res;
+    for (auto [src, dst, what] : {std::make_tuple(&post_scale_, &ps, "post_scale"),
+                                  std::make_tuple(&post_shift_, &pb, "post_shift")}) {
+        if (src->has_value()) {
+            check_hip_f32(**src, what);
+            TORCH_CHECK((*src)->device() == x_.device(), "po2q: ", what, " must be on the input's device");
+            TORCH_CHECK((*src)->numel() == yshape[1], "po2q: ", what, " must have ", yshape[1], " elements, got ",
+                        (*src)->numel());
+            *dst = (*src)->contiguous();
+        }
+    }
+    if (residual_.has_value()) {
+        check_hip_bf16(*residual_, "residual");
+        TORCH_CHECK(residual_->device() == x_.device(), "po2q: residual must be on the input's device");
+        TORCH_CHECK(residual_->sizes() == at::IntArrayRef(yshape), "po2q: residual shape ", residual_->sizes(),
+                    " does not match the output ", at::IntArrayRef(yshape));
+        res = residual_->contiguous();
+    }
     const DeviceGuard guard(x_.device());
     const at::Tensor x = x_.contiguous(), w = w_.contiguous();
     at::Tensor y = at::empty(yshape, x.options());
@@ -286,11 +309,43 @@ at::Tensor qconv2d_bf16(const at::Tensor& x_, const at::Tensor& w_, const c10::o
     TORCH_CHECK(wsb > 0, last_error());
     at::Tensor ws = at::empty({(int64_t)wsb}, x.options().dtype(at::kByte));
     auto ptr = [](const at::Tensor& t) { return reinterpret_cast<uint16_t*>(t.data_ptr()); };
-    const int st = po2q_qconv2d_bf16(ptr(x), ptr(w), bias.has_value() ? ptr(*bias) : nullptr, ptr(y), g[0], g[1], g[2],
-                                     g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11], g[12], g[13], (int)bits,
-                                     (int)fsr, (int)mode, ws.data_ptr(), wsb, stream_of(x));
+    const uint16_t* bp = bias.has_value() ? ptr(*bias) : nullptr;
+    const int st =
+        fused ? po2q_qconv2d_fused_bf16(ptr(x), ptr(w), bp, ptr(y), g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8],
+                                        g[9], g[10], g[11], g[12], g[13], (int)bits, (int)fsr, (int)mode, opt_ptr(ps),
+                                        opt_ptr(pb), res.has_value() ? ptr(*res) : nullptr, (int)act, ws.data_ptr(),
+                                        wsb, stream_of(x))
+              : po2q_qconv2d_bf16(ptr(x), ptr(w), bp, ptr(y), g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9],
+                                  g[10], g[11], g[12], g[13], (int)bits, (int)fsr, (int)mode, ws.data_ptr(), wsb,
+                                  stream_of(x));
     TORCH_CHECK(st == 0, last_error());
     return y;
+}
+
+at::Tensor qconv2d_bf16(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias,
+                        at::IntArrayRef stride, at::IntArrayRef padding, at::IntArrayRef dilation, int64_t groups,
+                        int64_t bits, int64_t mode, int64_t fsr) {
+    return qconv2d_bf16_impl(x, w, bias, stride, padding, dilation, groups, bits, mode, fsr, false, c10::nullopt,
+                             c10::nullopt, c10::nullopt, 0);
+}
+
+// act(bn(conv(x)) + residual) of a model in bf16 in the conv's launch (po2q_qconv2d_fused_bf16):
+// post_scale / post_shift fp32 [K], residual bf16 like the output, one rounding to bf16 at the end
+at::Tensor qconv2d_fused_bf16(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias,
+                              at::IntArrayRef stride, at::IntArrayRef padding, at::IntArrayRef dilation, int64_t groups,
+                              int64_t bits, int64_t mode, int64_t fsr, const c10::optional<at::Tensor>& post_scale,
+                              const c10::optional<at::Tensor>& post_shift, const c10::optional<at::Tensor>& residual,
+                              int64_t act) {
+    TORCH_CHECK(act >= 0 && act <= 3, "po2q: unknown activation ", act);
+    return qconv2d_bf16_impl(x, w, bias, stride, padding, dilation, groups, bits, mode, fsr, true, post_scale,
+                             post_shift, residual, act);
+}
+
+at::Tensor qconv2d_fused_bf16_meta(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>&,
+                                   at::IntArrayRef stride, at::IntArrayRef padding, at::IntArrayRef dilation, int64_t,
+                                   int64_t, int64_t, int64_t, const c10::optional<at::Tensor>&,
+                                   const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&, int64_t) {
+    return at::empty(conv_out_shape(x, w, stride, padding, dilation), x.options().dtype(at::kBFloat16));
 }
 
 at::Tensor qconv2d_bf16_meta(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>&,
@@ -857,6 +912,9 @@ TORCH_LIBRARY(po2q, m) {
           "Tensor? residual=None, int act3=0, int[] plans=[]) -> Tensor");
     m.def("qconv2d_bf16(Tensor x, Tensor w, Tensor? bias, int[] stride, int[] padding, int[] dilation, int groups, "
           "int bits, int mode, int fsr=1) -> Tensor");
+    m.def("qconv2d_fused_bf16(Tensor x, Tensor w, Tensor? bias, int[] stride, int[] padding, int[] dilation, "
+          "int groups, int bits, int mode, int fsr, Tensor? post_scale, Tensor? post_shift, Tensor? residual, "
+          "int act) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(po2q, CUDA, m) {  // the HIP device (PyTorch-ROCm dispatches HIP tensors under CUDA)
@@ -873,6 +931,7 @@ TORCH_LIBRARY_IMPL(po2q, CUDA, m) {  // the HIP device (PyTorch-ROCm dispatches 
     m.impl("qconv2d_packed", &qconv2d_packed);
     m.impl("qconv2d_ir", &qconv2d_ir);
     m.impl("qconv2d_bf16", &qconv2d_bf16);
+    m.impl("qconv2d_fused_bf16", &qconv2d_fused_bf16);
 }
 
 TORCH_LIBRARY_IMPL(po2q, Meta, m) {
@@ -889,4 +948,5 @@ TORCH_LIBRARY_IMPL(po2q, Meta, m) {
     m.impl("qconv2d_packed", &qconv2d_packed_meta);
     m.impl("qconv2d_ir", &qconv2d_ir_meta);
     m.impl("qconv2d_bf16", &qconv2d_bf16_meta);
+    m.impl("qconv2d_fused_bf16", &qconv2d_fused_bf16_meta);
 }

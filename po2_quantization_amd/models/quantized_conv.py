@@ -20,7 +20,8 @@ gradient through the native conv kernels (strided layers on zero-inserted dy), t
 gradient through the native fp32 wgrad kernels, dense and depthwise (_QConv2dFn.backward).
 HIP inputs are fp32, or bf16 for the forward-only native bf16 conv (po2q_qconv2d_bf16: po2 / po2+ /
 no quantizer, groups 1 or depthwise; BatchNorm, residual and activation then run as the module
-sequence does); anything else raises, there is no silent fallback on the GPU.  CPU
+sequence does, or, with BF16_FUSED_EPILOGUE, in the conv kernel's store: po2q_qconv2d_fused_bf16);
+anything else raises, there is no silent fallback on the GPU.  CPU
 inputs take the reference's own torch arithmetic (`_torch_forward`: the product's restated
 quantizers + F.conv2d, never the oracle, never libpo2q), as the reference runs on any device.
 
@@ -203,8 +204,47 @@ def fold_bn(bn):
     return s, t
 
 
+def fold_bn_f32(bn):
+    """fold_bn in fp32 whatever the BatchNorm's dtype, for the fused bf16 epilogue
+    (po2q_qconv2d_fused_bf16 takes fp32 post_scale / post_shift): the statistics and affine parameters
+    are upcast first, then rsqrt(var + eps) * weight and bias - mean * s are computed in fp32.  An fp32
+    BatchNorm gives fold_bn's own tensors.  Cached on the module under a key of its own: the marker
+    tells this fold apart from the one fold_bn caches in the module's dtype."""
+    if bn.running_var.dtype == torch.float32 and (not bn.affine or bn.weight.dtype == torch.float32):
+        return fold_bn(bn)
+    key = ("f32",) + _fold_key(bn)
+    hit = getattr(bn, "_po2q_fold_f32", None)
+    if hit is not None and hit[0] == key:
+        return hit[1], hit[2]
+    with torch.no_grad():
+        s = torch.rsqrt(bn.running_var.float() + bn.eps)
+        if bn.affine:
+            s = s * bn.weight.float()
+            t = bn.bias.float() - bn.running_mean.float() * s
+        else:
+            t = -bn.running_mean.float() * s
+    bn._po2q_fold_f32 = (key, s, t)
+    return s, t
+
+
 # Inference fusion switch (tools/model_bench.py times both sides).
 INFERENCE_FUSION = True
+# The bf16 fused calls' epilogue in the conv kernel's store (po2q_qconv2d_fused_bf16: BatchNorm folded in
+# fp32, residual and activation on the fp32 accumulator, ONE rounding to bf16) in place of torch's
+# elementwise kernels after the conv.  Off by default: the module sequence rounds to bf16 after the
+# conv, after the BatchNorm and after the add, so the fused result is closer to the exact one but not
+# the sequence's bits (tools/bf16_conv_bench.py --fused times both sides).
+BF16_FUSED_EPILOGUE = False
+
+
+def bf16_fused_input(x):
+    """True when the fused calls take this input to the fused bf16 entry (BF16_FUSED_EPILOGUE)."""
+    return BF16_FUSED_EPILOGUE and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
+
+
+def _has_hooks(conv):
+    # a forward hook is owed the conv's own output: such a module runs conv, hooks, then the epilogue
+    return bool(conv._forward_hooks) or bool(conv._forward_pre_hooks)
 
 
 def can_fuse(*mods):
@@ -374,6 +414,22 @@ class QuantizedConv2d(nn.Conv2d):
                               self.bits, mode, 1)
         return y.squeeze(0) if unbatched else y
 
+    def _bf16_fused(self, input, bn, act, residual):
+        """fused() on a 4-D bf16 HIP input with BF16_FUSED_EPILOGUE: one po2q_qconv2d_fused_bf16 call, the
+        weight and mode chosen as _bf16_forward chooses them, the BatchNorm folded in fp32."""
+        if self.padding_mode != "zeros":
+            raise RuntimeError("po2q: only padding_mode='zeros' is supported (the reference uses the default)")
+        _require_no_grad(input, self.weight, self.bias)
+        weight, mode = self.weight, "none"
+        if self.quantize_fn is not None:
+            mode = NATIVE_MODES.get(self.quantize_fn)
+            if mode is None:
+                weight, mode = self.quantize_fn.apply(self.weight, self.bits), "none"
+        ps, pb = fold_bn_f32(bn) if bn is not None else (None, None)
+        return _lib.qconv2d_fused_bf16(input, weight, self.bias, self.stride, self._padding(input), self.dilation,
+                                       self.groups, self.bits, mode, 1, post_scale=ps, post_shift=pb,
+                                       residual=residual, act=act or "none")
+
     def forward(self, input):
         # reference quantized_conv.py:32-38
         if not input.is_cuda:
@@ -394,7 +450,10 @@ class QuantizedConv2d(nn.Conv2d):
         'relu6' | 'silu'."""
         if not input.is_cuda:  # CPU: the reference's module sequence (conv -> bn -> + residual -> act)
             return _torch_epilogue(self(input), bn, act, residual)
-        if input.dtype == torch.bfloat16:  # the native bf16 conv, then the module sequence's own bf16 roundings
+        if input.dtype == torch.bfloat16:
+            if bf16_fused_input(input) and not _has_hooks(self):
+                return self._bf16_fused(input, bn, act, residual)
+            # the native bf16 conv, then the module sequence's own bf16 roundings
             return _torch_epilogue(self(input), bn, act, residual)
         if self.padding_mode != "zeros":
             raise RuntimeError("po2q: only padding_mode='zeros' is supported (the reference uses the default)")
@@ -447,12 +506,20 @@ def plain_conv(conv, x):
 def plain_conv_fused(conv, x, bn=None, act=None, residual=None):
     """An unquantized nn.Conv2d (the reference's stems and last 1x1 convs: resnet.py:99-102,
     mobilenet.py:41-50, mobile_vit.py:41-48) with the eval BatchNorm / activation after it, as
-    ONE native call of the fp32 path (mode "none": exact fp32 products, fp32 accumulation)."""
+    ONE native call of the fp32 path (mode "none": exact fp32 products, fp32 accumulation); a bf16
+    input takes the bf16 conv and the module sequence, or the fused bf16 entry (BF16_FUSED_EPILOGUE)."""
     if not x.is_cuda:
         return _torch_epilogue(conv(x), bn, act, residual)
     if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
         raise RuntimeError("po2q: fused plain conv needs numeric zero padding")
-    if x.dtype == torch.bfloat16:  # the native bf16 conv, then the module sequence's own bf16 roundings
+    if x.dtype == torch.bfloat16:
+        if bf16_fused_input(x) and not _has_hooks(conv):
+            _require_no_grad(x, conv.weight, conv.bias)
+            ps, pb = fold_bn_f32(bn) if bn is not None else (None, None)
+            return _lib.qconv2d_fused_bf16(x, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation,
+                                           conv.groups, 4, "none", 1, post_scale=ps, post_shift=pb,
+                                           residual=residual, act=act or "none")
+        # the native bf16 conv (and the module's hooks), then the module sequence's own bf16 roundings
         return _torch_epilogue(_plain_conv_bf16(conv, x), bn, act, residual)
     ps, pb = fold_bn(bn) if bn is not None else (None, None)
     return _lib.qconv2d_fused(x, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups, 4,

@@ -19,8 +19,8 @@ import torch.nn as nn
 
 from .. import _lib
 from ..utils.quantizers import NATIVE_MODES
-from .quantized_conv import (QuantizedConv2d, batched_packs, can_fuse, fold_bn, plain_conv, plain_conv_fused,
-                             run_fused_sequence)
+from .quantized_conv import (QuantizedConv2d, batched_packs, bf16_fused_input, can_fuse, fold_bn, plain_conv,
+                             plain_conv_fused, run_fused_sequence)
 
 
 class BasicBlock(nn.Module):
@@ -145,8 +145,9 @@ class ResNet(nn.Module):
 
     def forward(self, x):
         with batched_packs(self, x):  # eval: the single-conv layers' weight packs as batched launches
-            if can_fuse(self.bn1) and x.is_cuda and x.dtype == torch.float32:
+            if can_fuse(self.bn1) and x.is_cuda and (x.dtype == torch.float32 or bf16_fused_input(x)):
                 # the unquantized stem conv + bn1 + relu (resnet.py:99-102, 191) as one native fp32 call
+                # (a bf16 input with BF16_FUSED_EPILOGUE: one fused bf16 call)
                 x = plain_conv_fused(self.conv1, x, bn=self.bn1, act="relu")
             else:
                 x = self.relu(self.bn1(plain_conv(self.conv1, x)))  # native forward + backward

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from .models import quantized_conv
 from .models.model import get_model
 from .utils.quantizers import quantize_model, quantizer_dict
 
@@ -94,7 +95,9 @@ def evaluate_seed(model_type: str, num_classes: int, image_size, seed_dir: str, 
     bf16 = dtype == torch.bfloat16
     quantizers = {k: q for k, q in quantizer_dict.items() if not (bf16 and k in ("lin", "lin+"))}
     if bf16:
-        log("dtype bf16: lin / lin+ rows left out (no bf16 lin quantizer)")
+        epilogue = ("fused into the conv kernel (po2q_qconv2d_fused_bf16)" if quantized_conv.BF16_FUSED_EPILOGUE
+                    else "torch BatchNorm / add / activation after the conv")
+        log("dtype bf16: lin / lin+ rows left out (no bf16 lin quantizer); epilogue: " + epilogue)
     rows: List[Row] = []
     model = get_model(model_type=model_type, num_classes=num_classes, quantize_fn=None, bits=4,
                       image_size=image_size)
@@ -144,9 +147,11 @@ def tensor_loader(data_file: str, batch_size: int):
 
 
 def main(model_type: str, dataset: str, data_file: str, batch_size: int = 128, train_dir: str = "./train",
-         results_dir: str = "./results", skip_qat: bool = False, dtype: str = "fp32") -> None:
+         results_dir: str = "./results", skip_qat: bool = False, dtype: str = "fp32",
+         bf16_fused_epilogue: bool = False) -> None:
     """test.py:58-164 with the evaluation set from data_file."""
     assert dtype in DTYPES, "invalid dtype"
+    assert not bf16_fused_epilogue or dtype == "bf16", "--bf16-fused-epilogue needs --dtype bf16"
     assert torch.cuda.is_available(), "invalid hardware"
     assert model_type in ["resnet20", "resnet32", "resnet44", "resnet56", "mobilenet", "mobilevit"], \
         "invalid model type"
@@ -159,11 +164,16 @@ def main(model_type: str, dataset: str, data_file: str, batch_size: int = 128, t
     work_dir = f"{train_dir}/{dataset}/{model_type}"
     results_work_dir = f"{results_dir}/{dataset}/{model_type}"
     Path(results_work_dir).mkdir(parents=True, exist_ok=True)
-    for seed_dir in sorted(glob.glob(f"{work_dir}/*")):
-        seed = os.path.basename(seed_dir)
-        rows = evaluate_seed(model_type, num_classes, image_size, seed_dir, loader, device, skip_qat,
-                             dtype=DTYPES[dtype])
-        write_results(f"{results_work_dir}/{seed}.csv", rows)
+    saved = quantized_conv.BF16_FUSED_EPILOGUE
+    quantized_conv.BF16_FUSED_EPILOGUE = bool(bf16_fused_epilogue)  # for this run
+    try:
+        for seed_dir in sorted(glob.glob(f"{work_dir}/*")):
+            seed = os.path.basename(seed_dir)
+            rows = evaluate_seed(model_type, num_classes, image_size, seed_dir, loader, device, skip_qat,
+                                 dtype=DTYPES[dtype])
+            write_results(f"{results_work_dir}/{seed}.csv", rows)
+    finally:
+        quantized_conv.BF16_FUSED_EPILOGUE = saved
 
 
 def arg_parser():
@@ -179,9 +189,13 @@ def arg_parser():
     ap.add_argument("--skip_qat", action="store_true")
     ap.add_argument("--dtype", choices=sorted(DTYPES), default="fp32",
                     help="evaluate the models and their inputs in this dtype (bf16: model.bfloat16())")
+    ap.add_argument("--bf16-fused-epilogue", action="store_true",
+                    help="with --dtype bf16: BatchNorm, residual and activation in the conv kernel's store "
+                         "(models.quantized_conv.BF16_FUSED_EPILOGUE), one rounding to bf16 per layer")
     return ap
 
 
 if __name__ == "__main__":
     a = arg_parser().parse_args()
-    main(a.model_type, a.dataset, a.data_file, a.batch_size, a.train_dir, a.results_dir, a.skip_qat, a.dtype)
+    main(a.model_type, a.dataset, a.data_file, a.batch_size, a.train_dir, a.results_dir, a.skip_qat, a.dtype,
+         a.bf16_fused_epilogue)
