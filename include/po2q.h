@@ -233,6 +233,47 @@ int po2q_qconv2d_fused_bf16(const uint16_t* x, const uint16_t* w, const uint16_t
                             void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The two halves of po2q_qconv2d_bf16 / po2q_qconv2d_fused_bf16 apart, so that the weight staging
+ * of many layers is a few launches in front of a forward instead of two per layer.
+ *
+ * po2q_qconv2d_bf16_pack_batch quantizes and packs n weight tensors.  Job i is w[i] (bf16
+ * [K, C/groups, R, S], 2-byte aligned is enough) with geometry[14 * i .. 14 * i + 13] = N, C, H, W,
+ * K, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups (the argument order of
+ * po2q_qconv2d_bf16), bits[i], fsr[i], mode[i], and workspace[i] of workspace_bytes[i] >=
+ * po2q_qconv2d_bf16_workspace_bytes of that job.  Jobs may differ in everything.  It leaves in
+ * workspace[i] exactly what po2q_qconv2d_bf16 leaves there before it launches its conv: the same
+ * device code computes max|w| and the quantized fragments, so the bits are the same.
+ * Launches: at most 2 * ceil(n / 36), one max|w| and one quantize + pack launch per group of 36
+ * jobs; a group whose jobs are all mode none has no max|w| launch.
+ * Every job is validated as po2q_qconv2d_bf16 validates its arguments (same codes, same messages,
+ * followed by " (bf16 pack batch job i)") before the first launch: if any job is invalid (a lin
+ * mode, grouped but not depthwise, depthwise above 5x5, a tile that does not fit LDS, bits out of
+ * range, a NULL weight or workspace, a short workspace) nothing is launched and no workspace is
+ * touched.  n == 0 returns PO2Q_OK without a launch; n < 0 or a NULL array with n > 0 is
+ * PO2Q_ERR_INVALID.
+ *
+ * po2q_qconv2d_packed_bf16 runs the conv alone from such a workspace, with the epilogue arguments
+ * of po2q_qconv2d_fused_bf16 (all NULL and PO2Q_ACT_NONE: the plain kernel).  The geometry, bits
+ * and mode must be those the workspace was packed for; w is not read.  Enqueued on one stream
+ * after the batch entry, y is bit for bit what po2q_qconv2d_bf16 / po2q_qconv2d_fused_bf16 write.
+ * Validation is that of po2q_qconv2d_fused_bf16 (a NULL x, y or workspace and an unknown act are
+ * PO2Q_ERR_INVALID, a short workspace PO2Q_ERR_WORKSPACE); every error returns before any launch
+ * and leaves y untouched.
+ * Both are asynchronous, allocate no device memory and are safe under graph capture.
+ */
+int po2q_qconv2d_bf16_pack_batch(int n, const uint16_t* const* w, const int64_t* geometry,
+                                 const int* bits, const int* fsr, const int* mode,
+                                 void* const* workspace, const size_t* workspace_bytes, void* stream);
+int po2q_qconv2d_packed_bf16(const uint16_t* x, const uint16_t* bias, uint16_t* y,
+                             int64_t N, int64_t C, int64_t H, int64_t W,
+                             int64_t K, int64_t R, int64_t S,
+                             int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
+                             int64_t dil_h, int64_t dil_w, int64_t groups,
+                             int bits, int fsr, int mode,
+                             const float* post_scale, const float* post_shift, const uint16_t* residual, int act,
+                             const void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Kernel autotuning, the counterpart of the reference's
  * torch.backends.cudnn.benchmark = True (train.py:33, test.py:31): times every
  * candidate plan for this problem on these buffers (synchronises the stream;

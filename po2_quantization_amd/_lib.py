@@ -9,7 +9,7 @@ planning / tuning / diagnostic entry points, the two-enqueue SplitConv, and ever
 PO2Q_LIB points at another build of libpo2q.so (diagnostic builds).
 
 fp32 HIP tensors always run the native kernels: a missing library raises, there is no
-torch fallback for them.  bf16 HIP tensors have the forward-only qconv2d_bf16 (po2q_qconv2d_bf16) and qconv2d_fused_bf16 (po2q_qconv2d_fused_bf16).  The PO2 / PO2+ quantizer also takes fp64 and bf16 HIP tensors natively
+torch fallback for them.  bf16 HIP tensors have the forward-only qconv2d_bf16 (po2q_qconv2d_bf16) and qconv2d_fused_bf16 (po2q_qconv2d_fused_bf16), and their weight staging batched over layers (pack_batch_bf16 + qconv2d_packed_bf16).  The PO2 / PO2+ quantizer also takes fp64 and bf16 HIP tensors natively
 (the reference preserves dtype); other inputs (CPU tensors, fp16, ...) take
 restated_quantize, the reference formula written as torch ops in the input's dtype and device.
 """
@@ -73,6 +73,8 @@ EXPORTS = (
     "po2q_qconv2d_bf16",
     "po2q_qconv2d_fused_bf16",
     "po2q_qconv2d_bf16_describe",
+    "po2q_qconv2d_bf16_pack_batch",
+    "po2q_qconv2d_packed_bf16",
 )
 
 # Kernel autotuning on the first call per conv problem, the counterpart of
@@ -200,6 +202,12 @@ def load():
     L.po2q_qconv2d_fused_bf16.argtypes = [p, p, p, p] + [i64] * 14 + [i32, i32, i32, p, p, p, i32, p, sz, p]
     L.po2q_qconv2d_bf16_describe.restype = i32
     L.po2q_qconv2d_bf16_describe.argtypes = [i64] * 14 + [i32, i32, i32, ctypes.c_char_p, sz]
+    L.po2q_qconv2d_bf16_pack_batch.restype = i32
+    L.po2q_qconv2d_bf16_pack_batch.argtypes = [i32, ctypes.POINTER(p), ctypes.POINTER(i64), ctypes.POINTER(i32),
+                                               ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(p),
+                                               ctypes.POINTER(sz), p]
+    L.po2q_qconv2d_packed_bf16.restype = i32
+    L.po2q_qconv2d_packed_bf16.argtypes = [p, p, p] + [i64] * 14 + [i32, i32, i32, p, p, p, i32, p, sz, p]
     _lib = L
     return L
 
@@ -463,15 +471,8 @@ def qconv2d_bf16(x, w, bias=None, stride=1, padding=0, dilation=1, groups=1, bit
     return y
 
 
-def qconv2d_fused_bf16(x, w, bias=None, stride=1, padding=0, dilation=1, groups=1, bits=4, mode="po2", fsr=1,
-                       post_scale=None, post_shift=None, residual=None, act="none"):
-    """qconv2d_bf16 with the eval epilogue in the conv kernel's store (po2q_qconv2d_fused_bf16):
-        y = bf16(act((acc + bias) * post_scale[k] + post_shift[k] + residual))
-    on the kernel's fp32 accumulator, one rounding to bf16 at the end.  post_scale / post_shift: fp32 [K]
-    (an eval BatchNorm folded in fp32 by the caller) or None; residual: a bf16 tensor of y's shape or
-    None (it may not alias x); act: "none" | "relu" | "relu6" | "silu".  Forward only."""
-    args, yshape = _bf16_geometry(x, w, bias, stride, padding, dilation, groups)
-    mode_id = MODES[mode]
+def _bf16_epilogue(x, yshape, post_scale, post_shift, residual):
+    """The checks of the fused bf16 epilogue's tensors; returns ([post_scale, post_shift], residual), contiguous."""
     ext = []
     for t, what in ((post_scale, "post_scale"), (post_shift, "post_shift")):
         if t is not None:
@@ -491,6 +492,19 @@ def qconv2d_fused_bf16(x, w, bias=None, stride=1, padding=0, dilation=1, groups=
             raise Po2qError("po2q: residual shape %s does not match the output %s"
                             % (list(residual.shape), list(yshape)))
         rc = residual.contiguous()
+    return ext, rc
+
+
+def qconv2d_fused_bf16(x, w, bias=None, stride=1, padding=0, dilation=1, groups=1, bits=4, mode="po2", fsr=1,
+                       post_scale=None, post_shift=None, residual=None, act="none"):
+    """qconv2d_bf16 with the eval epilogue in the conv kernel's store (po2q_qconv2d_fused_bf16):
+        y = bf16(act((acc + bias) * post_scale[k] + post_shift[k] + residual))
+    on the kernel's fp32 accumulator, one rounding to bf16 at the end.  post_scale / post_shift: fp32 [K]
+    (an eval BatchNorm folded in fp32 by the caller) or None; residual: a bf16 tensor of y's shape or
+    None (it may not alias x); act: "none" | "relu" | "relu6" | "silu".  Forward only."""
+    args, yshape = _bf16_geometry(x, w, bias, stride, padding, dilation, groups)
+    mode_id = MODES[mode]
+    ext, rc = _bf16_epilogue(x, yshape, post_scale, post_shift, residual)
     if yshape[0] == 0:
         return torch.empty(yshape, dtype=torch.bfloat16, device=x.device)
     O = ops()
@@ -781,6 +795,49 @@ def qconv2d_packed(x, w, workspace, bias=None, stride=1, padding=0, dilation=1, 
     return _op_call(O.qconv2d_packed, xc, wc, workspace, bc, list(args[7:9]), list(args[9:11]), list(args[11:13]),
                     args[13], int(bits), MODES[mode], int(fsr), PRECISIONS[precision], -1 if saved is None else int(saved),
                     post_scale, post_shift, residual, ACTS[act])
+
+
+def _per_layer(v, n, what):
+    if isinstance(v, (list, tuple)):
+        if len(v) != n:
+            raise Po2qError("po2q: pack_batch_bf16: one %s per layer (or one for all)" % what)
+        return list(v)
+    return [v] * n
+
+
+def pack_batch_bf16(layers, bits=4, mode="po2", fsr=1):
+    """The weight staging (max|w|, quantize + pack) of several qconv2d_bf16 / qconv2d_fused_bf16 calls as
+    batched launches in front of them (torch.ops.po2q.qconv2d_pack_batch_bf16 ->
+    po2q_qconv2d_bf16_pack_batch: at most 2 * ceil(n / 36) launches for n layers, where the calls
+    themselves take two per layer).  layers = [(w, x_shape, stride, padding, dilation, groups)]; bits,
+    mode ("none" / "po2" / "po2+") and fsr are one value for all layers or one per layer.  Returns one
+    workspace per layer for qconv2d_packed_bf16.  Any layer the bf16 conv does not take raises before
+    anything is launched."""
+    O = ops()
+    if O is None:
+        raise Po2qError("po2q: pack_batch_bf16 needs the operator library (PO2Q_LIB selects another build)")
+    n = len(layers)
+    geom, ws = [], []
+    for w, x_shape, stride, padding, dilation, groups in layers:
+        _require_hip_bf16(w, "weight")
+        geom += _layer_geometry(x_shape, stride, padding, dilation, groups)
+        ws.append(w)
+    return _op_call(O.qconv2d_pack_batch_bf16, ws, geom, [int(b) for b in _per_layer(bits, n, "bits")],
+                    [MODES[m] for m in _per_layer(mode, n, "mode")], [int(f) for f in _per_layer(fsr, n, "fsr")])
+
+
+def qconv2d_packed_bf16(x, w, workspace, bias=None, stride=1, padding=0, dilation=1, groups=1, bits=4, mode="po2",
+                        fsr=1, post_scale=None, post_shift=None, residual=None, act="none"):
+    """qconv2d_bf16 / qconv2d_fused_bf16 from a workspace pack_batch_bf16 filled for this layer (the conv
+    and its epilogue only: po2q_qconv2d_packed_bf16).  Bit for bit their result.  Of w only the shape is
+    used; bits and mode must be those the workspace was packed with."""
+    O = ops()
+    if O is None:
+        raise Po2qError("po2q: qconv2d_packed_bf16 needs the operator library (PO2Q_LIB selects another build)")
+    args, yshape = _bf16_geometry(x, w, bias, stride, padding, dilation, groups)
+    ext, rc = _bf16_epilogue(x, yshape, post_scale, post_shift, residual)
+    return _op_call(O.qconv2d_packed_bf16, x, w, workspace, bias, list(args[7:9]), list(args[9:11]),
+                    list(args[11:13]), args[13], int(bits), MODES[mode], int(fsr), ext[0], ext[1], rc, ACTS[act])
 
 
 def ir_shape_supported(x_shape, Ch, Cout, stride, expand, mode="po2"):

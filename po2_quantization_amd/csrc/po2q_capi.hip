@@ -635,31 +635,83 @@ size_t po2q_qconv2d_bf16_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_
     return b16_workspace_bytes(p);
 }
 
-// po2q_qconv2d_bf16 (an empty epilogue) and po2q_qconv2d_fused_bf16: every check, then b16_run
-static int b16_conv(const uint16_t* x, const uint16_t* w, const uint16_t* bias, uint16_t* y, int64_t N, int64_t C,
-                    int64_t H, int64_t W, int64_t K, int64_t R, int64_t S, int64_t stride_h, int64_t stride_w,
-                    int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t groups, int bits, int fsr,
-                    int mode, const B16Epi& e, void* workspace, size_t workspace_bytes, void* stream) {
+// Every check of the bf16 conv entries, in one order for all of them: mode and bits, the pointers
+// (ptrs: none of the entry's required pointers is NULL), the activation, the geometry g[14] (the
+// argument order of po2q_qconv2d_bf16) and what the bf16 kernels do not take, then the workspace size.
+// Fills the plan; nothing is launched here.
+static int b16_validate(ConvPlan& p, bool ptrs, int act, const int64_t* g, int bits, int mode,
+                        size_t workspace_bytes) {
     if (!check_mode_bits(mode, bits, true)) return PO2Q_ERR_INVALID;
-    if (!x || !w || !y || !workspace) {
+    if (!ptrs) {
         set_error("po2q: null pointer");
         return PO2Q_ERR_INVALID;
     }
-    if (e.act < PO2Q_ACT_NONE || e.act > PO2Q_ACT_SILU) {
-        set_error("po2q: unknown activation " + std::to_string(e.act));
+    if (act < PO2Q_ACT_NONE || act > PO2Q_ACT_SILU) {
+        set_error("po2q: unknown activation " + std::to_string(act));
         return PO2Q_ERR_INVALID;
     }
-    ConvPlan p;
-    const int st =
-        b16_resolve(p, N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, bits, mode);
+    const int st = b16_resolve(p, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11], g[12],
+                               g[13], bits, mode);
     if (st) return st;
     const size_t need = b16_workspace_bytes(p);
     if (workspace_bytes < need) {
         set_error("po2q: conv workspace too small (need " + std::to_string(need) + " bytes)");
         return PO2Q_ERR_WORKSPACE;
     }
+    return PO2Q_OK;
+}
+
+// po2q_qconv2d_bf16 (an empty epilogue) and po2q_qconv2d_fused_bf16: every check, then b16_run
+static int b16_conv(const uint16_t* x, const uint16_t* w, const uint16_t* bias, uint16_t* y, int64_t N, int64_t C,
+                    int64_t H, int64_t W, int64_t K, int64_t R, int64_t S, int64_t stride_h, int64_t stride_w,
+                    int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t groups, int bits, int fsr,
+                    int mode, const B16Epi& e, void* workspace, size_t workspace_bytes, void* stream) {
+    const int64_t g[14] = {N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups};
+    ConvPlan p;
+    const int st = b16_validate(p, x && w && y && workspace, e.act, g, bits, mode, workspace_bytes);
+    if (st) return st;
     return hip_status(b16_run(p, x, w, bias, y, bits, fsr, mode, workspace, reinterpret_cast<hipStream_t>(stream), e),
                       "bf16 conv launch");
+}
+
+int po2q_qconv2d_bf16_pack_batch(int n, const uint16_t* const* w, const int64_t* geometry, const int* bits,
+                                 const int* fsr, const int* mode, void* const* workspace,
+                                 const size_t* workspace_bytes, void* stream) {
+    if (n < 0 || (n > 0 && (!w || !geometry || !bits || !fsr || !mode || !workspace || !workspace_bytes))) {
+        set_error("po2q: bf16 pack batch: null arrays");
+        return PO2Q_ERR_INVALID;
+    }
+    if (n == 0) return PO2Q_OK;
+    // every job is checked before the first launch: an invalid one leaves every workspace untouched
+    std::vector<ConvPlan> plans((size_t)n);
+    std::vector<B16PackReq> reqs((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const int st = b16_validate(plans[i], w[i] && workspace[i], PO2Q_ACT_NONE, geometry + 14 * (int64_t)i, bits[i],
+                                    mode[i], workspace_bytes[i]);
+        if (st) {
+            set_error(std::string(po2q_last_error()) + " (bf16 pack batch job " + std::to_string(i) + ")");
+            return st;
+        }
+        reqs[i] = B16PackReq{&plans[i], w[i], workspace[i], bits[i], fsr[i], mode[i]};
+    }
+    return hip_status(b16_pack_batch(n, reqs.data(), reinterpret_cast<hipStream_t>(stream)), "bf16 pack batch launch");
+}
+
+int po2q_qconv2d_packed_bf16(const uint16_t* x, const uint16_t* bias, uint16_t* y, int64_t N, int64_t C, int64_t H,
+                             int64_t W, int64_t K, int64_t R, int64_t S, int64_t stride_h, int64_t stride_w,
+                             int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t groups, int bits,
+                             int fsr, int mode, const float* post_scale, const float* post_shift,
+                             const uint16_t* residual, int act, const void* workspace, size_t workspace_bytes,
+                             void* stream) {
+    (void)fsr;  // part of the pack (the exponent window), not of the conv
+    const int64_t g[14] = {N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups};
+    B16Epi e;
+    e.ps = post_scale; e.pb = post_shift; e.res = residual; e.act = act;
+    ConvPlan p;
+    const int st = b16_validate(p, x && y && workspace, act, g, bits, mode, workspace_bytes);
+    if (st) return st;
+    return hip_status(b16_run_packed(p, x, bias, y, workspace, reinterpret_cast<hipStream_t>(stream), e),
+                      "bf16 packed conv launch");
 }
 
 int po2q_qconv2d_bf16(const uint16_t* x, const uint16_t* w, const uint16_t* bias, uint16_t* y, int64_t N, int64_t C,

@@ -379,19 +379,28 @@ __global__ __launch_bounds__(kThreads) void conv_dw_b16(const uint16_t* __restri
 }
 
 // ---- weight staging: max|w| partials, then quantize + pack ---------------------------------
+// Each step is one __device__ body with two callers: the kernel of one weight tensor (b16_run) and
+// the batched kernel (b16_pack_batch: blockIdx.y = weight tensor).  `block` of `nblocks` is the
+// block's place among the blocks working on this tensor.
 constexpr int kB16Parts = 256;  // at most one partial per thread of the pack kernel's fold
 
-__global__ __launch_bounds__(kThreads) void absmax_b16(const uint16_t* __restrict__ w, int64_t n,
-                                                       uint32_t* __restrict__ partial) {
-    __shared__ uint32_t red[kThreads / 64];
+__device__ __forceinline__ void absmax_b16_body(const uint16_t* __restrict__ w, int64_t n,
+                                                uint32_t* __restrict__ partial, int block, int nblocks,
+                                                uint32_t* red) {
     uint32_t m = 0u;  // sign-cleared bit patterns order as NaN > inf > finite, as torch.max propagates NaN
-    const int64_t stride = (int64_t)gridDim.x * kThreads;
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) m = max(m, (uint32_t)(w[i] & 0x7fffu));
+    const int64_t stride = (int64_t)nblocks * kThreads;
+    for (int64_t i = (int64_t)block * kThreads + threadIdx.x; i < n; i += stride) m = max(m, (uint32_t)(w[i] & 0x7fffu));
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, off, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = max(max(red[0], red[1]), max(red[2], red[3]));
+    if (threadIdx.x == 0) partial[block] = max(max(red[0], red[1]), max(red[2], red[3]));
+}
+
+__global__ __launch_bounds__(kThreads) void absmax_b16(const uint16_t* __restrict__ w, int64_t n,
+                                                       uint32_t* __restrict__ partial) {
+    __shared__ uint32_t red[kThreads / 64];
+    absmax_b16_body(w, n, partial, (int)blockIdx.x, (int)gridDim.x, red);
 }
 
 struct PackB16Args {
@@ -403,10 +412,9 @@ struct PackB16Args {
     int nparts;
 };
 
-__global__ __launch_bounds__(kThreads) void pack_b16(const uint16_t* __restrict__ w,
-                                                     const uint32_t* __restrict__ partial,
-                                                     uint16_t* __restrict__ out, PackB16Args a) {
-    __shared__ uint32_t red[kThreads / 64];
+__device__ __forceinline__ void pack_b16_body(const uint16_t* __restrict__ w, const uint32_t* __restrict__ partial,
+                                              uint16_t* __restrict__ out, const PackB16Args& a, int block,
+                                              int nblocks, uint32_t* red) {
     uint16_t sb = 0;
     if (a.quant) {  // fold the partials: the scale max|w| as a bf16
         uint32_t m = ((int)threadIdx.x < a.nparts) ? partial[threadIdx.x] : 0u;
@@ -416,14 +424,14 @@ __global__ __launch_bounds__(kThreads) void pack_b16(const uint16_t* __restrict_
         __syncthreads();
         sb = (uint16_t)max(max(red[0], red[1]), max(red[2], red[3]));
     }
-    const int64_t stride = (int64_t)gridDim.x * kThreads;
+    const int64_t stride = (int64_t)nblocks * kThreads;
     if (!a.dense) {
-        for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < a.n; i += stride)
+        for (int64_t i = (int64_t)block * kThreads + threadIdx.x; i < a.n; i += stride)
             out[i] = a.quant ? quant_bf16(w[i], sb, a.mode, a.lo, a.hi) : w[i];
         return;
     }
     const int oct = a.CC / 8;
-    for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < a.nfrag; e += stride) {
+    for (int64_t e = (int64_t)block * kThreads + threadIdx.x; e < a.nfrag; e += stride) {
         const int lane = (int)(e & 63);
         int64_t r = e >> 6;
         const int nt = (int)(r % a.NT);
@@ -449,6 +457,45 @@ __global__ __launch_bounds__(kThreads) void pack_b16(const uint16_t* __restrict_
         reinterpret_cast<uint4*>(out)[e] =
             make_uint4(q[0] | (q[1] << 16), q[2] | (q[3] << 16), q[4] | (q[5] << 16), q[6] | (q[7] << 16));
     }
+}
+
+__global__ __launch_bounds__(kThreads) void pack_b16(const uint16_t* __restrict__ w,
+                                                     const uint32_t* __restrict__ partial,
+                                                     uint16_t* __restrict__ out, PackB16Args a) {
+    __shared__ uint32_t red[kThreads / 64];
+    pack_b16_body(w, partial, out, a, (int)blockIdx.x, (int)gridDim.x, red);
+}
+
+// Up to kB16Batch weight tensors in one launch of each step (blockIdx.y = tensor): the two or
+// three launches per layer of a forward become 2 * ceil(n / kB16Batch) in front of it.  A job
+// is what b16_run hands its own two kernels; jobs of one launch differ freely in geometry, bits,
+// fsr and mode.  A mode-none job (quant 0) has no max|w| step.  Blocks past a job's own grid
+// (nparts / nb, the grids of the single-tensor launches) exit at once.
+struct B16PackJob {
+    const uint16_t* w;  // 2-byte aligned only
+    uint32_t* partial;
+    uint16_t* out;
+    PackB16Args a;
+    int nb;  // pack blocks
+};
+constexpr int kB16Batch = 36;  // 36 x 104-byte jobs: 3.7 KB of kernel arguments (the limit is 4 KB)
+struct B16PackBatch {
+    B16PackJob job[kB16Batch];
+};
+static_assert(sizeof(B16PackBatch) <= 4096, "the batched bf16 pack kernels' arguments must fit the 4 KB kernel-argument limit");
+
+__global__ __launch_bounds__(kThreads) void absmax_b16_batch(B16PackBatch B) {
+    const B16PackJob& j = B.job[blockIdx.y];
+    if (!j.a.quant || (int)blockIdx.x >= j.a.nparts) return;  // block-uniform
+    __shared__ uint32_t red[kThreads / 64];
+    absmax_b16_body(j.w, j.a.n, j.partial, (int)blockIdx.x, j.a.nparts, red);
+}
+
+__global__ __launch_bounds__(kThreads) void pack_b16_batch(B16PackBatch B) {
+    const B16PackJob& j = B.job[blockIdx.y];
+    if ((int)blockIdx.x >= j.nb) return;  // block-uniform
+    __shared__ uint32_t red[kThreads / 64];
+    pack_b16_body(j.w, j.partial, j.out, j.a, (int)blockIdx.x, j.nb, red);
 }
 
 int cdiv(int a, int b) { return (a + b - 1) / b; }
@@ -595,11 +642,14 @@ void b16_describe(const ConvPlan& p, char* buf, size_t len) {
                  p.lds_bytes, (long long)p.blocks);
 }
 
-hipError_t b16_run(const ConvPlan& p, const uint16_t* x, const uint16_t* w, const uint16_t* bias, uint16_t* y, int bits,
-                   int fsr, int mode, void* workspace, hipStream_t s, const B16Epi& epi) {
-    uint32_t* partial = reinterpret_cast<uint32_t*>(workspace);
-    uint16_t* packed =
-        reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(workspace) + align256((size_t)kB16Parts * sizeof(uint32_t)));
+namespace {
+
+uint16_t* b16_packed_ptr(void* workspace) {
+    return reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(workspace) + align256((size_t)kB16Parts * sizeof(uint32_t)));
+}
+
+// what the quantize + pack of one weight tensor is told: the plan's fragment layout and the window
+PackB16Args b16_pack_args(const ConvPlan& p, int bits, int fsr, int mode) {
     const int64_t nw = (int64_t)p.K * p.Cg * p.taps;
     PackB16Args pa;
     pa.C = p.Cg; pa.K = p.K; pa.taps = p.taps; pa.CC = p.CC; pa.NT = p.NT; pa.ksteps = p.steps;
@@ -612,16 +662,64 @@ hipError_t b16_run(const ConvPlan& p, const uint16_t* x, const uint16_t* w, cons
     pa.lo = pa.quant ? fsr - (1 << (bits - 1)) : 0;
     pa.hi = fsr - 1;
     pa.nparts = b16_parts(nw);
-    if (pa.quant) {
-        hipLaunchKernelGGL(absmax_b16, dim3(pa.nparts), dim3(kThreads), 0, s, w, nw, partial);
+    return pa;
+}
+
+int b16_pack_blocks(const PackB16Args& pa) {
+    const int64_t units = pa.dense ? pa.nfrag : pa.n;
+    return (int)std::min<int64_t>(1024, std::max<int64_t>(1, (units + kThreads - 1) / kThreads));
+}
+
+}  // namespace
+
+hipError_t b16_pack_batch(int n, const B16PackReq* reqs, hipStream_t s) {
+    for (int i0 = 0; i0 < n; i0 += kB16Batch) {
+        B16PackBatch B;
+        const int m = std::min(kB16Batch, n - i0);
+        int nbmax = 1, npmax = 0;
+        for (int i = 0; i < m; ++i) {
+            const B16PackReq& r = reqs[i0 + i];
+            B16PackJob& j = B.job[i];
+            j.w = r.w;
+            j.partial = reinterpret_cast<uint32_t*>(r.workspace);
+            j.out = b16_packed_ptr(r.workspace);
+            j.a = b16_pack_args(*r.plan, r.bits, r.fsr, r.mode);
+            j.nb = b16_pack_blocks(j.a);
+            nbmax = std::max(nbmax, j.nb);
+            if (j.a.quant) npmax = std::max(npmax, j.a.nparts);
+        }
+        if (npmax > 0) {  // a group of mode-none jobs alone has no max|w| launch
+            hipLaunchKernelGGL(absmax_b16_batch, dim3((unsigned)npmax, (unsigned)m), dim3(kThreads), 0, s, B);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(pack_b16_batch, dim3((unsigned)nbmax, (unsigned)m), dim3(kThreads), 0, s, B);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    const int64_t units = pa.dense ? pa.nfrag : nw;
-    const int pgrid = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (units + kThreads - 1) / kThreads));
-    hipLaunchKernelGGL(pack_b16, dim3(pgrid), dim3(kThreads), 0, s, w, partial, packed, pa);
-    hipError_t e = hipGetLastError();
+    return hipSuccess;
+}
+
+hipError_t b16_run(const ConvPlan& p, const uint16_t* x, const uint16_t* w, const uint16_t* bias, uint16_t* y, int bits,
+                   int fsr, int mode, void* workspace, hipStream_t s, const B16Epi& epi) {
+    uint32_t* partial = reinterpret_cast<uint32_t*>(workspace);
+    const PackB16Args pa = b16_pack_args(p, bits, fsr, mode);
+    if (pa.quant) {
+        hipLaunchKernelGGL(absmax_b16, dim3(pa.nparts), dim3(kThreads), 0, s, w, pa.n, partial);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(pack_b16, dim3(b16_pack_blocks(pa)), dim3(kThreads), 0, s, w, partial, b16_packed_ptr(workspace),
+                       pa);
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    return b16_run_packed(p, x, bias, y, workspace, s, epi);
+}
+
+// The conv alone, from a workspace b16_run's pack launches or b16_pack_batch filled
+hipError_t b16_run_packed(const ConvPlan& p, const uint16_t* x, const uint16_t* bias, uint16_t* y,
+                          const void* workspace, hipStream_t s, const B16Epi& epi) {
+    const uint16_t* packed = b16_packed_ptr(const_cast<void*>(workspace));
     if (p.kind == KIND_DW_BF16) {
         DwB16Args d;
         d.C = p.C; d.H = p.H; d.W = p.W; d.P = p.P; d.Q = p.Q; d.R = p.R; d.S = p.S;

@@ -263,6 +263,19 @@ size_t b16_workspace_bytes(const ConvPlan& p);
 void b16_describe(const ConvPlan& p, char* buf, size_t len);
 hipError_t b16_run(const ConvPlan& p, const uint16_t* x, const uint16_t* w, const uint16_t* bias, uint16_t* y,
                    int bits, int fsr, int mode, void* workspace, hipStream_t s, const B16Epi& e = B16Epi{});
+// The two halves of b16_run apart (po2q_qconv2d_bf16_pack_batch / po2q_qconv2d_packed_bf16).
+// b16_pack_batch leaves in each request's workspace what b16_run leaves there before its conv: the
+// max|w| and quantize + pack steps of n weight tensors (validated b16_plan plans, each with its own
+// bits / fsr / mode) in at most 2 * ceil(n / 36) launches; b16_run_packed enqueues the conv alone.
+struct B16PackReq {
+    const ConvPlan* plan;
+    const uint16_t* w;
+    void* workspace;  // >= b16_workspace_bytes(*plan)
+    int bits, fsr, mode;
+};
+hipError_t b16_pack_batch(int n, const B16PackReq* reqs, hipStream_t s);
+hipError_t b16_run_packed(const ConvPlan& p, const uint16_t* x, const uint16_t* bias, uint16_t* y,
+                          const void* workspace, hipStream_t s, const B16Epi& e = B16Epi{});
 
 // lin / lin+ quantizer (po2q_lin.hip): w, out [d0, d1, rs = d2*d3], one block per d1 channel
 hipError_t launch_quantize_lin(const float* w, float* out, int d0, int d1, int rs, int bits, int num_iters, int plus,

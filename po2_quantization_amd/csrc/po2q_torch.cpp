@@ -29,6 +29,8 @@
 //                        bf16, one bf16 MFMA pass (po2q_qconv2d_bf16); forward only
 //   po2q::qconv2d_fused_bf16  the same + eval BatchNorm affine (fp32), bf16 residual add and activation
 //                        in the conv kernel's store, one rounding to bf16 (po2q_qconv2d_fused_bf16)
+//   po2q::qconv2d_pack_batch_bf16 / po2q::qconv2d_packed_bf16  the bf16 forward's weight staging of many
+//                        layers as batched launches, and each conv (+ epilogue) from its pack
 // Meta kernels give the output shapes (FX / torch.compile tracing, fake tensors).
 // Errors are TORCH_CHECK -> RuntimeError, as F.conv2d raises for bad arguments.
 #include <ATen/ATen.h>
@@ -351,6 +353,148 @@ at::Tensor qconv2d_fused_bf16_meta(const at::Tensor& x, const at::Tensor& w, con
 at::Tensor qconv2d_bf16_meta(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>&,
                              at::IntArrayRef stride, at::IntArrayRef padding, at::IntArrayRef dilation, int64_t,
                              int64_t, int64_t, int64_t) {
+    return at::empty(conv_out_shape(x, w, stride, padding, dilation), x.options().dtype(at::kBFloat16));
+}
+
+// ---- batched weight staging of the bf16 forward (po2q_qconv2d_bf16_pack_batch / _packed_bf16) ----
+// geometry: 11 ints per layer, as qconv2d_pack_batch takes them (N C H W of the layer's input, stride
+// h/w, padding h/w, dilation h/w, groups); bits / mode / fsr: one int per layer
+std::array<int64_t, 14> bf16_layer_geometry(at::IntArrayRef geometry, int64_t i, const at::Tensor& w) {
+    const int64_t* g = geometry.data() + 11 * i;
+    return {g[0], g[1], g[2], g[3], w.size(0), w.size(2), w.size(3), g[4], g[5], g[6], g[7], g[8], g[9], g[10]};
+}
+
+void check_bf16_batch_lists(at::TensorList weights, at::IntArrayRef geometry, at::IntArrayRef bits,
+                            at::IntArrayRef mode, at::IntArrayRef fsr) {
+    const int64_t n = (int64_t)weights.size();
+    TORCH_CHECK((int64_t)geometry.size() == 11 * n, "po2q: pack_batch_bf16: 11 geometry ints per weight");
+    TORCH_CHECK((int64_t)bits.size() == n && (int64_t)mode.size() == n && (int64_t)fsr.size() == n,
+                "po2q: pack_batch_bf16: one bits, mode and fsr per weight");
+    for (int64_t i = 0; i < n; ++i) TORCH_CHECK(weights[i].dim() == 4, "po2q: pack_batch_bf16: 4-D weights");
+}
+
+size_t bf16_job_workspace(const std::array<int64_t, 14>& g, int64_t bits, int64_t fsr, int64_t mode, int64_t i) {
+    const size_t b = po2q_qconv2d_bf16_workspace_bytes(g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10],
+                                                       g[11], g[12], g[13], (int)bits, (int)fsr, (int)mode);
+    TORCH_CHECK(b > 0, last_error(), " (bf16 pack batch job ", i, ")");
+    return b;
+}
+
+std::vector<at::Tensor> qconv2d_pack_batch_bf16(at::TensorList weights, at::IntArrayRef geometry, at::IntArrayRef bits,
+                                                at::IntArrayRef mode, at::IntArrayRef fsr) {
+    check_bf16_batch_lists(weights, geometry, bits, mode, fsr);
+    const int64_t n = (int64_t)weights.size();
+    if (n == 0) return {};
+    std::vector<at::Tensor> wc(n);
+    std::vector<int64_t> off(n + 1, 0), geo(14 * n);
+    std::vector<size_t> wsb(n);
+    for (int64_t i = 0; i < n; ++i) {
+        check_hip_bf16(weights[i], "weight");
+        TORCH_CHECK(weights[i].device() == weights[0].device(), "po2q: pack_batch_bf16: weights on one device");
+        wc[i] = weights[i].contiguous();
+        const auto g = bf16_layer_geometry(geometry, i, wc[i]);
+        TORCH_CHECK(wc[i].size(1) * g[13] == g[1], "po2q: pack_batch_bf16: weight ", i, " of size ", wc[i].sizes(),
+                    " does not match ", g[1], " input channels in ", g[13], " groups");
+        std::copy(g.begin(), g.end(), geo.begin() + 14 * i);
+        wsb[i] = bf16_job_workspace(g, bits[i], fsr[i], mode[i], i);
+        off[i + 1] = off[i] + ((int64_t)wsb[i] + 255) / 256 * 256;
+    }
+    const DeviceGuard guard(weights[0].device());
+    at::Tensor all = at::empty({off[n]}, weights[0].options().dtype(at::kByte));
+    std::vector<at::Tensor> out(n);
+    std::vector<const uint16_t*> wp(n);
+    std::vector<void*> sp(n);
+    std::vector<int> b(n), f(n), m(n);
+    for (int64_t i = 0; i < n; ++i) {
+        out[i] = all.narrow(0, off[i], (int64_t)wsb[i]);
+        wp[i] = reinterpret_cast<const uint16_t*>(wc[i].data_ptr());
+        sp[i] = out[i].data_ptr();
+        b[i] = (int)bits[i]; f[i] = (int)fsr[i]; m[i] = (int)mode[i];
+    }
+    const int st = po2q_qconv2d_bf16_pack_batch((int)n, wp.data(), geo.data(), b.data(), f.data(), m.data(), sp.data(),
+                                                wsb.data(), stream_of(weights[0]));
+    TORCH_CHECK(st == 0, last_error());
+    return out;
+}
+
+std::vector<at::Tensor> qconv2d_pack_batch_bf16_meta(at::TensorList weights, at::IntArrayRef geometry,
+                                                     at::IntArrayRef bits, at::IntArrayRef mode, at::IntArrayRef fsr) {
+    check_bf16_batch_lists(weights, geometry, bits, mode, fsr);
+    std::vector<at::Tensor> out;
+    for (int64_t i = 0; i < (int64_t)weights.size(); ++i)
+        out.push_back(at::empty({(int64_t)bf16_job_workspace(bf16_layer_geometry(geometry, i, weights[i]), bits[i],
+                                                             fsr[i], mode[i], i)},
+                                weights[i].options().dtype(at::kByte)));
+    return out;
+}
+
+// the conv (and its fused epilogue) from a workspace qconv2d_pack_batch_bf16 filled; of w (as
+// qconv2d_packed takes it) only the shape is used: its values are in the workspace
+at::Tensor qconv2d_packed_bf16(const at::Tensor& x_, const at::Tensor& w_, const at::Tensor& workspace,
+                               const c10::optional<at::Tensor>& bias_, at::IntArrayRef stride, at::IntArrayRef padding,
+                               at::IntArrayRef dilation, int64_t groups, int64_t bits, int64_t mode, int64_t fsr,
+                               const c10::optional<at::Tensor>& post_scale_, const c10::optional<at::Tensor>& post_shift_,
+                               const c10::optional<at::Tensor>& residual_, int64_t act) {
+    TORCH_CHECK(act >= 0 && act <= 3, "po2q: unknown activation ", act);
+    check_hip_bf16(x_, "input");
+    check_hip_bf16(w_, "weight");
+    const std::vector<int64_t> yshape = conv_out_shape(x_, w_, stride, padding, dilation);
+    TORCH_CHECK(x_.device() == w_.device(), "po2q: input and weight must be on the same device");
+    const at::IntArrayRef wshape = w_.sizes();
+    TORCH_CHECK(workspace.is_cuda() && workspace.scalar_type() == at::kByte && workspace.is_contiguous() &&
+                    workspace.device() == x_.device(),
+                "po2q: packed_bf16: the workspace must be a contiguous uint8 tensor on the input's device");
+    TORCH_CHECK(groups > 0, "po2q: non-positive groups is not supported");
+    TORCH_CHECK(wshape[1] * groups == x_.size(1), "po2q: Given groups=", groups, ", weight of size ", wshape,
+                ", expected input", x_.sizes(), " to have ", wshape[1] * groups, " channels, but got ", x_.size(1),
+                " channels instead");
+    const int64_t g[14] = {x_.size(0), x_.size(1), x_.size(2), x_.size(3), wshape[0], wshape[2], wshape[3],
+                           pick(stride, 0, "stride"), pick(stride, 1, "stride"), pick(padding, 0, "padding"),
+                           pick(padding, 1, "padding"), pick(dilation, 0, "dilation"), pick(dilation, 1, "dilation"),
+                           groups};
+    c10::optional<at::Tensor> bias, ps, pb, res;
+    if (bias_.has_value()) {
+        check_hip_bf16(*bias_, "bias");
+        TORCH_CHECK(bias_->device() == x_.device(), "po2q: bias must be on the input's device");
+        TORCH_CHECK(bias_->numel() == g[4], "po2q: bias must have ", g[4], " elements");
+        bias = bias_->contiguous();
+    }
+    for (auto [src, dst, what] : {std::make_tuple(&post_scale_, &ps, "post_scale"),
+                                  std::make_tuple(&post_shift_, &pb, "post_shift")}) {
+        if (src->has_value()) {
+            check_hip_f32(**src, what);
+            TORCH_CHECK((*src)->device() == x_.device(), "po2q: ", what, " must be on the input's device");
+            TORCH_CHECK((*src)->numel() == yshape[1], "po2q: ", what, " must have ", yshape[1], " elements, got ",
+                        (*src)->numel());
+            *dst = (*src)->contiguous();
+        }
+    }
+    if (residual_.has_value()) {
+        check_hip_bf16(*residual_, "residual");
+        TORCH_CHECK(residual_->device() == x_.device(), "po2q: residual must be on the input's device");
+        TORCH_CHECK(residual_->sizes() == at::IntArrayRef(yshape), "po2q: residual shape ", residual_->sizes(),
+                    " does not match the output ", at::IntArrayRef(yshape));
+        res = residual_->contiguous();
+    }
+    const DeviceGuard guard(x_.device());
+    const at::Tensor x = x_.contiguous();
+    at::Tensor y = at::empty(yshape, x.options());
+    if (yshape[0] == 0) return y;
+    auto ptr = [](const at::Tensor& t) { return reinterpret_cast<uint16_t*>(t.data_ptr()); };
+    const int st = po2q_qconv2d_packed_bf16(ptr(x), bias.has_value() ? ptr(*bias) : nullptr, ptr(y), g[0], g[1], g[2],
+                                            g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11], g[12], g[13],
+                                            (int)bits, (int)fsr, (int)mode, opt_ptr(ps), opt_ptr(pb),
+                                            res.has_value() ? ptr(*res) : nullptr, (int)act, workspace.data_ptr(),
+                                            (size_t)workspace.numel(), stream_of(x));
+    TORCH_CHECK(st == 0, last_error());
+    return y;
+}
+
+at::Tensor qconv2d_packed_bf16_meta(const at::Tensor& x, const at::Tensor& w, const at::Tensor&,
+                                    const c10::optional<at::Tensor>&, at::IntArrayRef stride, at::IntArrayRef padding,
+                                    at::IntArrayRef dilation, int64_t, int64_t, int64_t, int64_t,
+                                    const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&,
+                                    const c10::optional<at::Tensor>&, int64_t) {
     return at::empty(conv_out_shape(x, w, stride, padding, dilation), x.options().dtype(at::kBFloat16));
 }
 
@@ -915,6 +1059,10 @@ TORCH_LIBRARY(po2q, m) {
     m.def("qconv2d_fused_bf16(Tensor x, Tensor w, Tensor? bias, int[] stride, int[] padding, int[] dilation, "
           "int groups, int bits, int mode, int fsr, Tensor? post_scale, Tensor? post_shift, Tensor? residual, "
           "int act) -> Tensor");
+    m.def("qconv2d_pack_batch_bf16(Tensor[] weights, int[] geometry, int[] bits, int[] mode, int[] fsr) -> Tensor[]");
+    m.def("qconv2d_packed_bf16(Tensor x, Tensor w, Tensor workspace, Tensor? bias, int[] stride, int[] padding, "
+          "int[] dilation, int groups, int bits, int mode, int fsr=1, Tensor? post_scale=None, "
+          "Tensor? post_shift=None, Tensor? residual=None, int act=0) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(po2q, CUDA, m) {  // the HIP device (PyTorch-ROCm dispatches HIP tensors under CUDA)
@@ -932,6 +1080,8 @@ TORCH_LIBRARY_IMPL(po2q, CUDA, m) {  // the HIP device (PyTorch-ROCm dispatches 
     m.impl("qconv2d_ir", &qconv2d_ir);
     m.impl("qconv2d_bf16", &qconv2d_bf16);
     m.impl("qconv2d_fused_bf16", &qconv2d_fused_bf16);
+    m.impl("qconv2d_pack_batch_bf16", &qconv2d_pack_batch_bf16);
+    m.impl("qconv2d_packed_bf16", &qconv2d_packed_bf16);
 }
 
 TORCH_LIBRARY_IMPL(po2q, Meta, m) {
@@ -949,4 +1099,6 @@ TORCH_LIBRARY_IMPL(po2q, Meta, m) {
     m.impl("qconv2d_ir", &qconv2d_ir_meta);
     m.impl("qconv2d_bf16", &qconv2d_bf16_meta);
     m.impl("qconv2d_fused_bf16", &qconv2d_fused_bf16_meta);
+    m.impl("qconv2d_pack_batch_bf16", &qconv2d_pack_batch_bf16_meta);
+    m.impl("qconv2d_packed_bf16", &qconv2d_packed_bf16_meta);
 }

@@ -20,7 +20,8 @@ gradient through the native conv kernels (strided layers on zero-inserted dy), t
 gradient through the native fp32 wgrad kernels, dense and depthwise (_QConv2dFn.backward).
 HIP inputs are fp32, or bf16 for the forward-only native bf16 conv (po2q_qconv2d_bf16: po2 / po2+ /
 no quantizer, groups 1 or depthwise; BatchNorm, residual and activation then run as the module
-sequence does, or, with BF16_FUSED_EPILOGUE, in the conv kernel's store: po2q_qconv2d_fused_bf16);
+sequence does, or, with BF16_FUSED_EPILOGUE, in the conv kernel's store: po2q_qconv2d_fused_bf16; an
+eval forward batches the layers' weight staging like an fp32 one: BATCHED_PACKS);
 anything else raises, there is no silent fallback on the GPU.  CPU
 inputs take the reference's own torch arithmetic (`_torch_forward`: the product's restated
 quantizers + F.conv2d, never the oracle, never libpo2q), as the reference runs on any device.
@@ -270,6 +271,10 @@ def can_fuse(*mods):
 # weight still re-quantized in every forward.  The first forward of a model at an input shape
 # records which layers do that and at which shapes; later forwards at that shape pack them
 # up front.  False: every layer packs its own weight (A/B runs).
+# A bf16 forward (po2q_qconv2d_bf16) does the same with its own pair of entries: the first forward
+# records its QuantizedConv2d layers, and later forwards issue the max|w| and quantize + pack launches
+# of those that run their own weight (po2 / po2+ / no quantizer) as one _lib.pack_batch_bf16 call up
+# front (_ForwardPacksBf16), bit for bit the per-layer result.
 BATCHED_PACKS = True
 # The batched packs run inline on the forward's stream: a side stream overlapping the stem measured
 # slower in the graphed model lines (config 3 521k -> 493k img/s, config 5 13.77k -> 13.47k; the fork /
@@ -279,13 +284,16 @@ BATCHED_PACKS = True
 _tls = threading.local()
 
 
-def _session(module):
-    """The calling thread's active _ForwardPacks when `module` belongs to the model that opened it."""
+def _session(module, dtype=torch.float32):
+    """The calling thread's active session when `module` belongs to the model that opened it and the
+    session is one of `dtype` forwards (_ForwardPacks: fp32, _ForwardPacksBf16: bf16)."""
     sess = getattr(_tls, "packs", None)
-    return sess if sess is not None and id(module) in sess.owned else None
+    return sess if sess is not None and sess.dtype == dtype and id(module) in sess.owned else None
 
 
 class _ForwardPacks:
+    dtype = torch.float32
+
     def __init__(self, model, layers):
         self.recording = [] if layers is None else None
         self.owned = {id(m) for m in model.modules()}
@@ -314,6 +322,55 @@ class _ForwardPacks:
         return hit
 
 
+def _bf16_mode(conv):
+    """The bf16 conv's mode for a layer's own weight: "none" without a quantizer, "po2" / "po2+"; None for
+    any other quantize_fn (its Q(w) is a temporary of the forward: such a layer packs for itself)."""
+    return "none" if conv.quantize_fn is None else NATIVE_MODES.get(conv.quantize_fn)
+
+
+class _ForwardPacksBf16:
+    """The session of a bf16 forward: the recorded QuantizedConv2d layers' max|w| and quantize + pack
+    launches (two per layer in po2q_qconv2d_bf16, one in mode none) as ONE _lib.pack_batch_bf16 call
+    up front, each layer with its own (bits, mode); the layers then run qconv2d_packed_bf16.
+
+    The record is [(layer, geometry)] in call order and carries no quantizer settings: every session
+    reads each recorded layer's bits and quantizer as they are now and packs for those (a layer whose
+    quantizer has no bf16 mode sits the session out), so a changed setting needs no new record and no
+    walk over the model's modules to notice it.  A launch-bound eval forward is host-bound when run
+    eagerly: the two module walks of the fp32 session's prologue cost more there than the launches the
+    packs save (tools/bf16_packs_bench.py), so only the recording forward walks the model (`owned`);
+    later sessions own exactly the layers they packed."""
+    dtype = torch.bfloat16
+
+    def __init__(self, model, layers):
+        self.recording = [] if layers is None else None
+        self.ws = {}
+        if layers is None:
+            self.owned = {id(m) for m in model.modules()}
+            return
+        jobs = {}
+        for m, g in layers:  # a module once, at its first call's geometry
+            mode = _bf16_mode(m)
+            if mode is not None and id(m) not in jobs:
+                jobs[id(m)] = (m, g, (m.bits, mode), m.weight)
+        self.owned = jobs
+        if not jobs:
+            return
+        ws = _lib.pack_batch_bf16([(w, g[0], g[1], g[2], g[3], g[4]) for _, g, _, w in jobs.values()],
+                                  [conf[0] for _, _, conf, _ in jobs.values()],
+                                  [conf[1] for _, _, conf, _ in jobs.values()])
+        for (m, g, conf, w), pack in zip(jobs.values(), ws):
+            self.ws[id(m)] = (g, w, pack, conf)
+
+    def lookup(self, conv, g, weight, mode):
+        """The pack of `conv` when it was made for this geometry, this weight tensor and the (bits, mode)
+        of this call; None otherwise (the layer then stages its own weight)."""
+        hit = self.ws.get(id(conv))
+        if hit is None or hit[0] != g or hit[1] is not weight or hit[3] != (conv.bits, mode):
+            return None
+        return hit
+
+
 # model -> {forward key: recorded layers}; weak, so a dropped model takes its records with it
 _RECORDS = weakref.WeakKeyDictionary()
 
@@ -322,18 +379,25 @@ _RECORDS = weakref.WeakKeyDictionary()
 def batched_packs(model, x):
     """Run a model's eval forward with its single-conv layers' weight packs batched (BATCHED_PACKS)."""
     if (not BATCHED_PACKS or getattr(_tls, "packs", None) is not None or torch.is_grad_enabled() or model.training
-            or not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32)):
+            or not (isinstance(x, torch.Tensor) and x.is_cuda
+                    and (x.dtype == torch.float32 or (x.dtype == torch.bfloat16 and x.dim() == 4)))):
         yield
         return
-    # the record holds which layers read a packed weight and with which plan; it depends on the
-    # layers' quantizer settings and precision as much as on the input shape
-    confs = tuple((m.bits, native_mode(m.quantize_fn), m.precision) for m in model.modules()
-                  if isinstance(m, QuantizedConv2d))
-    key = (tuple(x.shape), x.device, INFERENCE_FUSION, IR_FUSION, confs)
     rec = _RECORDS.get(model)
     if rec is None:  # keyed by the model object itself: DataParallel replicas (shallow __dict__ copies) get their own
         rec = _RECORDS[model] = {}
-    sess = _ForwardPacks(model, rec.get(key))
+    # the keys carry the input dtype and BF16_FUSED_EPILOGUE: a model moved between .float() and
+    # .bfloat16() at one input shape never reads the other dtype's record
+    if x.dtype == torch.bfloat16:
+        key = (tuple(x.shape), x.device, x.dtype, BF16_FUSED_EPILOGUE, INFERENCE_FUSION)
+        sess = _ForwardPacksBf16(model, rec.get(key))
+    else:
+        # the record holds which layers read a packed weight and with which plan; it depends on the
+        # layers' quantizer settings and precision as much as on the input shape
+        confs = tuple((m.bits, native_mode(m.quantize_fn), m.precision) for m in model.modules()
+                      if isinstance(m, QuantizedConv2d))
+        key = (tuple(x.shape), x.device, x.dtype, BF16_FUSED_EPILOGUE, INFERENCE_FUSION, IR_FUSION, confs)
+        sess = _ForwardPacks(model, rec.get(key))
     _tls.packs = sess
     try:
         yield
@@ -410,9 +474,29 @@ class QuantizedConv2d(nn.Conv2d):
                 weight, mode = self.quantize_fn.apply(self.weight, self.bits), "none"
         unbatched = input.dim() == 3
         x = input.unsqueeze(0) if unbatched else input
-        y = _lib.qconv2d_bf16(x, weight, self.bias, self.stride, self._padding(x), self.dilation, self.groups,
-                              self.bits, mode, 1)
+        y = self._bf16_packed(x, weight, mode)
+        if y is None:
+            y = _lib.qconv2d_bf16(x, weight, self.bias, self.stride, self._padding(x), self.dilation, self.groups,
+                                  self.bits, mode, 1)
         return y.squeeze(0) if unbatched else y
+
+    def _bf16_packed(self, x, weight, mode, **epilogue):
+        """Inside a bf16 batched_packs forward, a layer that runs its own weight: the recording forward
+        notes it (and returns None), later forwards run the conv from the session's pack
+        (qconv2d_packed_bf16) when it was made for this geometry, weight and (bits, mode).  None: the
+        caller makes today's call."""
+        sess = _session(self, torch.bfloat16) if x.dim() == 4 else None
+        if sess is None:
+            return None
+        g = (tuple(x.shape), tuple(self.stride), tuple(self._padding(x)), tuple(self.dilation), self.groups)
+        if sess.recording is not None:
+            sess.recording.append((self, g))
+            return None
+        hit = sess.lookup(self, g, weight, mode)  # (a non-native quantizer's temporary Q(w) is never the packed weight)
+        if hit is None:
+            return None
+        return _lib.qconv2d_packed_bf16(x, weight, hit[2], self.bias, g[1], g[2], g[3], g[4], self.bits, mode, 1,
+                                        **epilogue)
 
     def _bf16_fused(self, input, bn, act, residual):
         """fused() on a 4-D bf16 HIP input with BF16_FUSED_EPILOGUE: one po2q_qconv2d_fused_bf16 call, the
@@ -426,6 +510,9 @@ class QuantizedConv2d(nn.Conv2d):
             if mode is None:
                 weight, mode = self.quantize_fn.apply(self.weight, self.bits), "none"
         ps, pb = fold_bn_f32(bn) if bn is not None else (None, None)
+        y = self._bf16_packed(input, weight, mode, post_scale=ps, post_shift=pb, residual=residual, act=act or "none")
+        if y is not None:
+            return y
         return _lib.qconv2d_fused_bf16(input, weight, self.bias, self.stride, self._padding(input), self.dilation,
                                        self.groups, self.bits, mode, 1, post_scale=ps, post_shift=pb,
                                        residual=residual, act=act or "none")
