@@ -368,6 +368,20 @@ int po2q_qconv2d_wgrad_f32(const float* x, const float* dy, float* dw,
                            int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
                            int64_t dil_h, int64_t dil_w, int64_t groups,
                            void* workspace, size_t workspace_bytes, void* stream);
+/*
+ * Diagnostic: the kernel and plan po2q_qconv2d_wgrad_f32 would run for these arguments, as one
+ * line of key=value fields written to buf (truncated to len).  Host only (no HIP call); built
+ * from the plan the launch itself resolves:
+ *   "kind=wgrad_stream R=3 SH=1 KW=2 CW=2 vec=1 RB=8 nseg=32 nstrip=1 items=128 bpg=32 KG=16 CG=2"
+ *   "kind=wgrad_band R=3 S=3 BP=5 XR=9 QT=64 nqt=2 WT=68 KT=3 CT=2 lds=59776"
+ *   "kind=wgrad_dw RS=9 nslice=2 per_slice=5"
+ * Returns the status the launch would return for the geometry (po2q_last_error set): non-zero
+ * for an unsupported geometry and for one no plan fits.  Used by tests to name the kernel instance
+ * each shape reaches.
+ */
+int po2q_qconv2d_wgrad_describe(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t R, int64_t S,
+                                int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
+                                int64_t dil_h, int64_t dil_w, int64_t groups, char* buf, size_t len);
 
 /*
  * Zero insertion for strided input gradients (QAT backward, reference train.py:79-91): the input

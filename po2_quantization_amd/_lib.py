@@ -55,6 +55,7 @@ EXPORTS = (
     "po2q_qconv2d_plan_destroy",
     "po2q_qconv2d_wgrad_workspace_bytes",
     "po2q_qconv2d_wgrad_f32",
+    "po2q_qconv2d_wgrad_describe",
     "po2q_qconv2d_pair_supported",
     "po2q_qconv2d_pair_f32",
     "po2q_qconv2d_s2ds_supported",
@@ -206,6 +207,12 @@ def load():
     L.po2q_qconv2d_bf16_pack_batch.argtypes = [i32, ctypes.POINTER(p), ctypes.POINTER(i64), ctypes.POINTER(i32),
                                                ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(p),
                                                ctypes.POINTER(sz), p]
+    L.po2q_qconv2d_wgrad_workspace_bytes.restype = sz
+    L.po2q_qconv2d_wgrad_workspace_bytes.argtypes = [i64] * 14
+    L.po2q_qconv2d_wgrad_f32.restype = i32
+    L.po2q_qconv2d_wgrad_f32.argtypes = [p, p, p] + [i64] * 14 + [p, sz, p]
+    L.po2q_qconv2d_wgrad_describe.restype = i32
+    L.po2q_qconv2d_wgrad_describe.argtypes = [i64] * 14 + [ctypes.c_char_p, sz]
     L.po2q_qconv2d_packed_bf16.restype = i32
     L.po2q_qconv2d_packed_bf16.argtypes = [p, p, p] + [i64] * 14 + [i32, i32, i32, p, p, p, i32, p, sz, p]
     _lib = L
@@ -1019,13 +1026,31 @@ def conv_wgrad(x, gy, wshape, stride=1, padding=0, dilation=1, groups=1):
     return _op_call(O.conv_wgrad, x, gy, list(wshape), [sh, sw], [ph, pw], [dh, dw], int(groups))
 
 
-def wgrad_supported(wshape, groups):
+def wgrad_supported(wshape, groups, x_shape=None, stride=1, padding=0, dilation=1):
     """The native weight-gradient kernels cover dense 1x1 / 3x3 layers and depthwise layers
-    (groups == C == K) up to 5x5."""
+    (groups == C == K) up to 5x5.  With x_shape (and the conv's stride / padding / dilation) the
+    library is asked as well (po2q_qconv2d_wgrad_workspace_bytes, host only): a layer whose band
+    fits no plan -- a 3x3 with a large dilation on a wide image -- is not supported."""
     K, Cg, R, S = (int(v) for v in wshape)
     if int(groups) == 1:
-        return (R, S) in ((1, 1), (3, 3))
-    return Cg == 1 and K == int(groups) and R * S <= 25 and S <= 5
+        ok = (R, S) in ((1, 1), (3, 3))
+    else:
+        ok = Cg == 1 and K == int(groups) and R * S <= 25 and S <= 5
+    if not ok or x_shape is None:
+        return ok
+    N, C, H, W = (int(v) for v in x_shape)
+    return load().po2q_qconv2d_wgrad_workspace_bytes(N, C, H, W, K, R, S, *_pair(stride), *_pair(padding),
+                                                     *_pair(dilation), int(groups)) != 0
+
+
+def describe_wgrad(N, C, H, W, K, R, S, stride=1, padding=0, dilation=1, groups=1):
+    """The kernel and plan conv_wgrad runs for this shape (diagnostic text, po2q_qconv2d_wgrad_describe);
+    raises where conv_wgrad would."""
+    L = load()
+    buf = ctypes.create_string_buffer(512)
+    _check(L.po2q_qconv2d_wgrad_describe(N, C, H, W, K, R, S, *_pair(stride), *_pair(padding), *_pair(dilation),
+                                         int(groups), buf, 512))
+    return buf.value.decode()
 
 
 def dilate(x, stride, size):

@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <string>
 
 #include "../../include/po2q.h"
@@ -26,10 +27,12 @@ namespace po2q {
 struct DwWgradArgs {
     int N, C, H, W, P, Q, R, S, sh, sw, ph, pw, dh, dw;
     int nslice, per_slice;  // images per block
+    int RS;                 // tap slots of the kernel instance: 9 or kDwMaxTaps
 };
 
 constexpr int kDwThreads = 256;
 constexpr int kDwMaxTaps = 25;  // up to 5x5
+constexpr const char* kDwUnsupported = "po2q: depthwise wgrad: unsupported geometry (kernel up to 5x5, sizes < 2^31)";
 
 template <int RS>
 __global__ __launch_bounds__(kDwThreads) void dw_wgrad_partial(const float* __restrict__ x,
@@ -106,8 +109,8 @@ static bool dw_wgrad_setup(DwWgradArgs& a, size_t& part_bytes, int64_t N, int64_
     const int64_t ns = std::min<int64_t>(N, std::min(want, by_work));
     a.per_slice = (int)((N + ns - 1) / ns);
     a.nslice = (int)((N + a.per_slice - 1) / a.per_slice);
-    const int rs = R * S <= 9 ? 9 : kDwMaxTaps;
-    part_bytes = (size_t)C * a.nslice * rs * sizeof(float);
+    a.RS = R * S <= 9 ? 9 : kDwMaxTaps;
+    part_bytes = (size_t)C * a.nslice * a.RS * sizeof(float);
     return true;
 }
 
@@ -162,13 +165,25 @@ size_t po2q_dw_wgrad_workspace_bytes_internal(int64_t N, int64_t C, int64_t H, i
     return std::max<size_t>(part, 256);
 }
 
+int po2q_dw_wgrad_describe_internal(int64_t N, int64_t C, int64_t H, int64_t W, int64_t R, int64_t S, int64_t sh,
+                                    int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw, char* buf, size_t len) {
+    po2q::DwWgradArgs a;
+    size_t part;
+    if (!po2q::dw_wgrad_setup(a, part, N, C, H, W, R, S, sh, sw, ph, pw, dh, dw)) {
+        po2q::set_error(po2q::kDwUnsupported);
+        return PO2Q_ERR_UNSUPPORTED;
+    }
+    snprintf(buf, len, "kind=wgrad_dw RS=%d nslice=%d per_slice=%d", a.RS, a.nslice, a.per_slice);
+    return PO2Q_OK;
+}
+
 int po2q_dw_wgrad_f32_internal(const float* x, const float* dy, float* dwt, int64_t N, int64_t C, int64_t H,
                                int64_t W, int64_t R, int64_t S, int64_t sh, int64_t sw, int64_t ph, int64_t pw,
                                int64_t dh, int64_t dw, void* workspace, size_t workspace_bytes, void* stream) {
     po2q::DwWgradArgs a;
     size_t part;
     if (!po2q::dw_wgrad_setup(a, part, N, C, H, W, R, S, sh, sw, ph, pw, dh, dw)) {
-        po2q::set_error("po2q: depthwise wgrad: unsupported geometry (kernel up to 5x5, sizes < 2^31)");
+        po2q::set_error(po2q::kDwUnsupported);
         return PO2Q_ERR_UNSUPPORTED;
     }
     if (!x || !dy || !dwt || !workspace) {
@@ -181,7 +196,7 @@ int po2q_dw_wgrad_f32_internal(const float* x, const float* dy, float* dwt, int6
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     float* pp = reinterpret_cast<float*>(workspace);
-    const hipError_t e = R * S <= 9 ? po2q::launch_dw_wgrad_t<9>(a, x, dy, dwt, pp, s)
+    const hipError_t e = a.RS == 9 ? po2q::launch_dw_wgrad_t<9>(a, x, dy, dwt, pp, s)
                                     : po2q::launch_dw_wgrad_t<po2q::kDwMaxTaps>(a, x, dy, dwt, pp, s);
     if (e != hipSuccess) {
         po2q::set_error(std::string("po2q: depthwise wgrad launch: ") + hipGetErrorString(e));

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <climits>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <string>
 
@@ -559,8 +560,15 @@ size_t po2q_dw_wgrad_workspace_bytes_internal(int64_t N, int64_t C, int64_t H, i
 int po2q_dw_wgrad_f32_internal(const float* x, const float* dy, float* dwt, int64_t N, int64_t C, int64_t H,
                                int64_t W, int64_t R, int64_t S, int64_t sh, int64_t sw, int64_t ph, int64_t pw,
                                int64_t dh, int64_t dw, void* workspace, size_t workspace_bytes, void* stream);
+int po2q_dw_wgrad_describe_internal(int64_t N, int64_t C, int64_t H, int64_t W, int64_t R, int64_t S, int64_t sh,
+                                    int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw, char* buf, size_t len);
 
 static bool wgrad_depthwise(int64_t C, int64_t K, int64_t groups) { return groups > 1 && groups == C && K == C; }
+
+// status of a dense call whose wgrad_setup failed
+static int wgrad_setup_status(int64_t R, int64_t S, int64_t groups) {
+    return (groups != 1 || !((R == 3 && S == 3) || (R == 1 && S == 1))) ? PO2Q_ERR_UNSUPPORTED : PO2Q_ERR_INVALID;
+}
 
 size_t po2q_qconv2d_wgrad_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t R,
                                           int64_t S, int64_t stride_h, int64_t stride_w, int64_t pad_h,
@@ -586,7 +594,7 @@ int po2q_qconv2d_wgrad_f32(const float* x, const float* dy, float* dw, int64_t N
     po2q::WgradArgs a;
     size_t lds, part;
     if (!wgrad_setup(a, lds, part, N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups))
-        return (groups != 1 || !((R == 3 && S == 3) || (R == 1 && S == 1))) ? PO2Q_ERR_UNSUPPORTED : PO2Q_ERR_INVALID;
+        return wgrad_setup_status(R, S, groups);
     if (!x || !dy || !dw || !workspace) {
         po2q::set_error("po2q: null pointer");
         return PO2Q_ERR_INVALID;
@@ -606,5 +614,31 @@ int po2q_qconv2d_wgrad_f32(const float* x, const float* dy, float* dw, int64_t N
         po2q::set_error(std::string("po2q: wgrad launch: ") + hipGetErrorString(e));
         return PO2Q_ERR_HIP;
     }
+    return PO2Q_OK;
+}
+
+int po2q_qconv2d_wgrad_describe(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t R, int64_t S,
+                                int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h,
+                                int64_t dil_w, int64_t groups, char* buf, size_t len) {
+    if (!buf || len == 0) {
+        po2q::set_error("po2q: describe needs a buffer");
+        return PO2Q_ERR_INVALID;
+    }
+    if (wgrad_depthwise(C, K, groups))
+        return po2q_dw_wgrad_describe_internal(N, C, H, W, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, buf,
+                                               len);
+    po2q::WgradArgs a;
+    size_t lds, part;
+    if (!wgrad_setup(a, lds, part, N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups))
+        return wgrad_setup_status(R, S, groups);
+    const Wgrad2Choice c2 = wgrad2_choose(a);
+    if (c2.use)
+        snprintf(buf, len,
+                 "kind=wgrad_stream R=%d SH=%d KW=%d CW=%d vec=%d RB=%d nseg=%d nstrip=%d items=%d bpg=%d KG=%d CG=%d",
+                 c2.R, c2.SH, c2.KW, c2.CW, c2.vec ? 1 : 0, c2.a.RB, c2.a.nseg, c2.a.nstrip, c2.a.items, c2.a.bpg,
+                 c2.a.KG, c2.a.CG);
+    else
+        snprintf(buf, len, "kind=wgrad_band R=%d S=%d BP=%d XR=%d QT=%d nqt=%d WT=%d KT=%d CT=%d lds=%zu", a.R, a.S,
+                 a.BP, a.XR, a.QT, a.nqt, a.WT, a.KT, a.CT, lds);
     return PO2Q_OK;
 }

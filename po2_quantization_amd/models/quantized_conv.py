@@ -95,7 +95,8 @@ class _QConv2dFn(torch.autograd.Function):
                     fp32 reduction for depthwise layers;
           bias   -- sum of gy over N, P, Q.
         What no kernel covers (padding beyond dil * (R - 1), grouped non-depthwise weight
-        gradients, other kernel sizes) is issued as one aten.convolution_backward of Q(w)."""
+        gradients, other kernel sizes, a dilated layer whose weight gradient fits no plan) is issued
+        as one aten.convolution_backward of Q(w)."""
         x, weight, bias = ctx.saved_tensors
         stride, padding, dilation, groups, bits, mode = ctx.conf
         gy = gy.contiguous()
@@ -105,7 +106,7 @@ class _QConv2dFn(torch.autograd.Function):
         st, pad, dil = _lib._pair(stride), _lib._pair(padding), _lib._pair(dilation)
         padl = (dil[0] * (R - 1) - pad[0], dil[1] * (S - 1) - pad[1])
         native_x = NATIVE_BACKWARD and need_x and padl[0] >= 0 and padl[1] >= 0
-        native_w = NATIVE_BACKWARD and need_w and _lib.wgrad_supported(weight.shape, groups)
+        native_w = NATIVE_BACKWARD and need_w and _lib.wgrad_supported(weight.shape, groups, x.shape, st, pad, dil)
         gx = gw = gb = None
         lin = mode in ("lin", "lin+")
         qw = _lib.quantize_lin(weight.detach(), bits, mode == "lin+", LIN_NUM_ITERS) if lin and (need_x or need_w) else None

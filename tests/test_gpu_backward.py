@@ -23,7 +23,8 @@ def ref_grads(x, w, b, gy, qn, bits, stride, pad, groups=1, dil=1):
     qw = w if qn is None else _lib.quantize(w, bits, qn)
     gx, gw, gb = torch.ops.aten.convolution_backward(
         gy.double().cpu(), x.double().cpu(), qw.double().cpu(), None if b is None else [b.shape[0]],
-        [stride, stride], [pad, pad], [dil, dil], False, [0, 0], groups, [True, True, b is not None])
+        list(_lib._pair(stride)), list(_lib._pair(pad)), list(_lib._pair(dil)), False, [0, 0], groups,
+        [True, True, b is not None])
     return gx, gw, gb
 
 
@@ -220,3 +221,103 @@ def test_dilate_zero_insertion():
         h, w = min(sub.shape[2], 5), min(sub.shape[3], 4)
         ref[:, :, :h * st[0]:st[0], :w * st[1]:st[1]] = x[:, :, :h, :w]
         assert torch.equal(y, ref), st
+
+
+# ---- module backward geometry ---------------------------------------------------------------------
+# N, C, H, W, K, kernel, stride, padding, dilation, groups, bias, quantizer, x requires grad,
+# rise of ATEN_BACKWARD_CALLS (0: both gradients native; 1: one of them issued to aten)
+GEOMETRY = {
+    "stride(2,1)": (2, 16, 13, 14, 16, 3, (2, 1), 1, 1, 1, False, "po2", True, 0),
+    "padding(0,1)": (2, 16, 12, 12, 16, 3, 1, (0, 1), 1, 1, False, "po2", True, 0),
+    "dilation(1,2)": (2, 16, 12, 14, 16, 3, 1, (1, 2), (1, 2), 1, False, "po2", True, 0),
+    "3x3-pad0-stride1": (2, 16, 11, 12, 24, 3, 1, 0, 1, 1, False, "po2", True, 0),        # padl = 2
+    "3x3-pad0-stride2-odd": (2, 16, 13, 13, 24, 3, 2, 0, 1, 1, False, "po2+", True, 0),
+    "3x3-pad0-stride2-even": (2, 16, 12, 12, 24, 3, 2, 0, 1, 1, False, "po2", True, 0),   # a row / column dy never reaches
+    "1x3": (2, 16, 10, 12, 16, (1, 3), 1, (0, 1), 1, 1, False, "po2", True, 1),           # weight gradient by aten
+    "3x1": (2, 16, 10, 12, 16, (3, 1), 1, (1, 0), 1, 1, False, "po2+", True, 1),
+    "padding3": (2, 16, 8, 8, 16, 3, 1, 3, 1, 1, False, "po2", True, 1),                  # input gradient by aten
+    "depthwise-multiplier": (2, 8, 10, 10, 16, 3, 1, 1, 1, 8, False, "po2", True, 1),     # K = 2C: weight gradient by aten
+    "x-without-grad": (2, 16, 12, 12, 16, 3, 1, 1, 1, 1, True, "po2", False, 0),
+    "bias-stride2": (2, 16, 15, 15, 32, 3, 2, 1, 1, 1, True, "po2", True, 0),
+    # the weight gradient's band fits no plan at dilation 6 and Q = 64 (tests/_wgrad_cases.py NO_PLAN_D6):
+    # issued to aten; the input gradient is the native conv of a dilated 64-wide layer
+    "dilation6-no-wgrad-plan": (1, 16, 64, 64, 16, 3, 1, 6, 6, 1, False, "po2", True, 1),
+}
+
+
+@pytest.mark.parametrize("name", list(GEOMETRY))
+def test_module_backward_geometry_vs_torch_fp64(name):
+    """QuantizedConv2d.backward on unequal stride / padding / dilation pairs, padding 0 (input-gradient
+    padding 2), the aten fallbacks and an input that needs no gradient: against torch's fp64 CPU
+    convolution_backward of Q(w), with the number of aten fallbacks each layer takes."""
+    from po2_quantization_amd.models import quantized_conv as qc
+
+    N, C, H, W, K, ker, st, pad, dil, groups, bias, qn, need_x, aten = GEOMETRY[name]
+    g = torch.Generator().manual_seed(len(name) * 131 + C + K)
+    conv = QuantizedConv2d(C, K, ker, stride=st, padding=pad, dilation=dil, groups=groups, bias=bias,
+                           quantize_fn=quantizer_dict[qn], bits=4)
+    with torch.no_grad():
+        conv.weight.copy_(torch.randn(conv.weight.shape, generator=g) * 0.3)
+        if bias:
+            conv.bias.copy_(torch.randn(K, generator=g))
+    conv = conv.to(DEV)
+    x = torch.randn(N, C, H, W, generator=g).to(DEV).requires_grad_(need_x)
+    before = qc.ATEN_BACKWARD_CALLS
+    y = conv(x)
+    gy = torch.randn(y.shape, generator=g).to(DEV)
+    y.backward(gy)
+    assert qc.ATEN_BACKWARD_CALLS - before == aten
+    rx, rw, rb = ref_grads(x.detach(), conv.weight.detach(), conv.bias, gy, qn, 4, st, pad, groups, dil)
+    if need_x:
+        assert x.grad.shape == x.shape
+        assert nerr(x.grad, rx) <= CONV_TOL, nerr(x.grad, rx)
+    else:
+        assert x.grad is None
+    assert nerr(conv.weight.grad, rw) <= CONV_TOL, nerr(conv.weight.grad, rw)
+    if bias:
+        assert nerr(conv.bias.grad, rb) <= CONV_TOL, nerr(conv.bias.grad, rb)
+
+
+EXACT_GX = {  # N, C, H, W, K, stride, groups, quantizer
+    "3x3-stride1": (2, 16, 12, 12, 32, 1, 1, "po2"),
+    "3x3-stride2": (2, 16, 13, 13, 32, 2, 1, "po2"),     # zero-inserted dy
+    "depthwise": (2, 24, 12, 12, 24, 1, 24, "po2+"),
+}
+
+
+@pytest.mark.parametrize("name", list(EXACT_GX))
+def test_input_gradient_exact_on_small_integers(name):
+    """The input gradient with a zero error bar.  One weight is exactly 1.0 and the rest lie in (-1, 1),
+    so the scale is 1 and every 4-bit Q(w) is +-2^-k, k = 0..7 (po2 and po2+ alike: both return
+    2^e * sign(w) * scale, asserted below); dy is integers in [-4, 4].  Every term dy * Q(w) is then a
+    multiple of q = min |Q(w)| and every partial sum, in any order, a multiple of q of magnitude at most
+    sum |dy| |Q(w)| < 2^24 q (asserted): exact in fp32, and the bf16x3 split of an integer dy has an
+    exact high part and zero mid / low parts.  So the native gradient must EQUAL the fp64 reference."""
+    from po2_quantization_amd.models import quantized_conv as qc
+
+    N, C, H, W, K, st, groups, qn = EXACT_GX[name]
+    g = torch.Generator().manual_seed(K + st)
+    conv = QuantizedConv2d(C, K, 3, stride=st, padding=1, groups=groups, quantize_fn=quantizer_dict[qn], bits=4)
+    with torch.no_grad():
+        conv.weight.copy_(torch.rand(conv.weight.shape, generator=g) * 2 - 1)
+        conv.weight.view(-1)[5] = 1.0
+    conv = conv.to(DEV)
+    x = torch.randint(-4, 5, (N, C, H, W), generator=g).float().to(DEV).requires_grad_(True)
+    before = qc.ATEN_BACKWARD_CALLS
+    y = conv(x)
+    gy = torch.randint(-4, 5, y.shape, generator=g).float().to(DEV)
+    y.backward(gy)
+    assert qc.ATEN_BACKWARD_CALLS == before
+    qw = _lib.quantize(conv.weight.detach(), 4, qn).double().cpu()
+    mant, _ = torch.frexp(qw.abs())
+    assert bool((mant == 0.5).all()) and float(qw.abs().max()) == 1.0  # every Q(w) is +-2^-k
+    qmin = float(qw.abs().min())
+    assert qmin >= 2.0 ** -7
+    rx, _, _ = ref_grads(x.detach(), conv.weight.detach(), None, gy, qn, 4, st, 1, groups)
+    mag, _, _ = torch.ops.aten.convolution_backward(gy.double().cpu().abs(), x.detach().double().cpu(), qw.abs(), None,
+                                                    [st, st], [1, 1], [1, 1], False, [0, 0], groups,
+                                                    [True, False, False])
+    assert float(mag.max()) / qmin < 2 ** 24
+    assert torch.equal(rx.float().double(), rx)
+    print(name, "max |gx - ref| = %g" % float((x.grad.cpu().double() - rx).abs().max()))
+    assert torch.equal(x.grad.cpu().double(), rx)
