@@ -407,6 +407,12 @@ int po2q_dilate_f32(const float* src, float* dst, int64_t N, int64_t C, int64_t 
  * po2q_qconv2d_pair_supported: 1 when it takes the shape AND is the faster path (C = 16 with
  * W > 96, C = 32 with W > 48 -- PO2Q_PAIR_C32=0 turns C = 32 off; otherwise two single-conv
  * calls).
+ * C = 64 (ResNet56 stage 3 at 56 x 56): po2q_qconv2d_pair_f32 also takes 32 < W <= 64, W % 4 == 0, in
+ * the plain form only (biases; a BN affine, activation or residual returns PO2Q_ERR_UNSUPPORTED).
+ * Here the two weights are quantized + packed by one batched launch first, into a scratch buffer
+ * the library keeps per (device, stream): the first such call on a stream allocates it (145 KiB,
+ * never inside a graph capture).  po2q_qconv2d_pair_supported stays 0 for C = 64: stage 3 reaches
+ * the pair kernel through po2q_qconv2d_chain_f32.
  */
 int po2q_qconv2d_pair_supported(int64_t N, int64_t C, int64_t H, int64_t W, int bits, int fsr, int mode);
 int po2q_qconv2d_pair_f32(const float* x, const float* w1, const float* w2, float* y,
@@ -417,7 +423,7 @@ int po2q_qconv2d_pair_f32(const float* x, const float* w1, const float* w2, floa
                           void* stream);
 
 /*
- * A chain of n_layers quantized 3x3 / stride-1 / pad-1 C -> C convs on small images in ONE
+ * A chain of n_layers quantized 3x3 / stride-1 / pad-1 C -> C convs -- on small images in ONE
  * launch: the stride-1 run of a ResNet stage at CIFAR size -- consecutive
  * QuantizedConv2d.forward calls (models/quantized_conv.py:32-38) as models/resnet.py:55-71 /
  * 25-50 chain them, each with its BasicBlock's eval BN / ReLU / identity shortcut:
@@ -435,6 +441,16 @@ int po2q_qconv2d_pair_f32(const float* x, const float* w1, const float* w2, floa
  * 1 <= n_layers <= PO2Q_CHAIN_MAX_LAYERS, (H + 2)(W + 2) 6C bytes <= 160 KiB and H * W <= 1024
  * (C = 16), 256 (C = 32), 128 (C = 64) -- ResNet's CIFAR stages --, mode po2 / po2+ with the
  * exponent window inside bf16's range.
+ *
+ * A second geometry runs as a SEQUENCE of launches, not one: C = 64 with 32 < W <= 64, W % 4 == 0,
+ * any H, 2 <= n_layers <= PO2Q_CHAIN_MAX_LAYERS (ResNet56 stage 3 at 56 x 56).  One batched
+ * launch quantizes + packs every weight; then the layers run left to right, two consecutive
+ * plain layers (no BN affine, activation or residual, and the activation between them no
+ * residual source) as one conv-pair launch with the intermediate on chip, every other layer
+ * as the fused single conv po2q_qconv2d_fused_f32 runs (its tuned or heuristic plan).  The
+ * activations between launches rotate through two buffers of the workspace and y, so the
+ * workspace is 2 N C H W floats plus the packs; x must not alias y.  Nothing synchronises or
+ * allocates: safe under graph capture.  PO2Q_PAIR64=0 makes this geometry unsupported again.
  */
 #define PO2Q_CHAIN_MAX_LAYERS 24
 int po2q_qconv2d_chain_supported(int64_t N, int64_t C, int64_t H, int64_t W, int n_layers, int bits, int fsr,

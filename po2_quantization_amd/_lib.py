@@ -662,8 +662,9 @@ def pair_supported(x_shape, bits=4, mode="po2", fsr=1):
 
 def qconv2d_pair(x, w1, w2, bits=4, mode="po2", fsr=1, bias1=None, bias2=None, post_scale1=None, post_shift1=None,
                  act1="none", post_scale2=None, post_shift2=None, residual=None, act2="none"):
-    """Two chained quantized 3x3 / stride-1 / pad-1 convs (C -> C -> C channels, C = 16 or 32)
-    in one launch (po2q_qconv2d_pair_f32), the intermediate kept on chip:
+    """Two chained quantized 3x3 / stride-1 / pad-1 convs (C -> C -> C channels, C = 16 or 32; C = 64
+    with 32 < W <= 64 in the plain form: biases only) in one launch (po2q_qconv2d_pair_f32), the
+    intermediate kept on chip:
         h = act1((conv(x, Q(w1)) + bias1) * post_scale1 + post_shift1)
         y = act2((conv(h, Q(w2)) + bias2) * post_scale2 + post_shift2 + residual)
     -- qconv2d_fused twice, as a ResNet56 stage-1 / stage-2 BasicBlock chains them (resnet.py:55-71)."""
@@ -682,7 +683,8 @@ CHAIN_MAX_LAYERS = 24  # include/po2q.h PO2Q_CHAIN_MAX_LAYERS
 def chain_supported(x_shape, n_layers, bits=4, mode="po2", fsr=1):
     """Whether qconv2d_chain takes n_layers C -> C 3x3 / stride-1 convs on x of this shape
     (po2q_qconv2d_chain_supported: C in {16, 32, 64}, W % 4 == 0, the padded image's split planes
-    in LDS -- CIFAR sizes)."""
+    in LDS -- CIFAR sizes, one launch; or C = 64 with 32 < W <= 64 and at least 2 layers -- ResNet56
+    stage 3 at 56 x 56, a run of conv-pair launches, unless PO2Q_PAIR64=0)."""
     N, C, H, W = (int(v) for v in x_shape)
     return bool(load().po2q_qconv2d_chain_supported(N, C, H, W, int(n_layers), int(bits), int(fsr),
                                                      MODES[mode]))
@@ -690,8 +692,10 @@ def chain_supported(x_shape, n_layers, bits=4, mode="po2", fsr=1):
 
 def qconv2d_chain(x, weights, bits=4, mode="po2", fsr=1, biases=None, post_scales=None, post_shifts=None,
                   acts=None, res_from=None):
-    """len(weights) quantized 3x3 / stride-1 / pad-1 C -> C convs in ONE launch (po2q_qconv2d_chain_f32,
-    torch.ops.po2q.qconv2d_chain):
+    """len(weights) quantized 3x3 / stride-1 / pad-1 C -> C convs in one call (po2q_qconv2d_chain_f32,
+    torch.ops.po2q.qconv2d_chain) -- ONE launch at CIFAR sizes; at C = 64 with 32 < W <= 64 one batched
+    weight pack, then conv-pair launches for the consecutive plain layers and fused single convs for
+    the rest:
         a_0 = x;  a_{l+1} = act_l((conv(a_l, Q(w_l)) + bias_l) * post_scale_l + post_shift_l
                                   (+ a_{res_from[l]}));   returns a_L
     -- the stride-1 run of a ResNet stage at CIFAR size, QuantizedConv2d.forward after

@@ -1009,3 +1009,33 @@ int po2q_qconv2d_plan_describe(const po2q_conv_plan* plan, char* buf, size_t len
 }
 
 void po2q_qconv2d_plan_destroy(po2q_conv_plan* plan) { delete plan; }
+
+// ------------------------------------------------- the chain entry's single-conv layers --
+// (po2q_conv_chain.hip, the large C = 64 geometry: every layer its pair kernel does not take)
+namespace po2q {
+
+bool single_plan(ConvPlan& p, int64_t N, int64_t C, int64_t H, int64_t W, int bits, int fsr, int mode) {
+    return make_plan(p, N, C, H, W, C, 3, 3, 1, 1, 1, 1, 1, 1, 1, mode, bits, fsr, PO2Q_PREC_AUTO);
+}
+
+SingleWs single_ws(const ConvPlan& p, int mode) {
+    const WsLayout L = ws_layout(p, mode);
+    SingleWs w;
+    w.total = L.total;
+    w.scale_off = L.scale_off;
+    w.packed_off = L.packed_off;
+    w.batch = plan_packs_weight(p, mode) && is_bf16x3_kind(p.kind) && pack_batchable(p, mode) && L.nparts == 0;
+    return w;
+}
+
+size_t single_ws_max(int64_t N, int64_t C, int64_t H, int64_t W) {
+    // the layout does not depend on bits / fsr, and po2 and po2+ share it
+    return po2q_qconv2d_workspace_bytes(N, C, H, W, C, 3, 3, 1, 1, 1, 1, 1, 1, 1, 4, 1, PO2Q_MODE_PO2, PO2Q_PREC_AUTO);
+}
+
+int single_run(const ConvPlan& p, const float* x, const float* w, const float* bias, float* y, int bits, int fsr,
+               int mode, void* workspace, size_t workspace_bytes, hipStream_t s, const ConvEpi& e, bool packed) {
+    return run_plan(p, x, w, bias, y, bits, fsr, mode, workspace, workspace_bytes, s, e, packed ? RUN_CONV : RUN_ALL);
+}
+
+}  // namespace po2q

@@ -1,4 +1,4 @@
-// A chain of quantized 3x3 / stride-1 / pad-1 C -> C convs on SMALL images, all of them in ONE
+// A chain of quantized 3x3 / stride-1 / pad-1 C -> C convs.  On SMALL images all of them run in ONE
 // launch: the stride-1 run of a ResNet56 stage at CIFAR size (reference models/resnet.py:55-71,
 // 25-50; each conv QuantizedConv2d.forward, models/quantized_conv.py:32-38), with each layer's
 // eval BN affine, activation and the BasicBlock's identity shortcut in its store.
@@ -23,6 +23,12 @@
 // arithmetic as every bf16x3 kernel (exact +-2^e bf16 weights, exact 3-way split of the fp32
 // activations -- each layer's fp32 output re-split exactly --, fp32 accumulation on
 // v_mfma_f32_16x16x32_bf16).
+//
+// A second geometry, large C = 64 images (32 < W <= 64: ResNet56 stage 3 at 56 x 56), runs the same
+// entry as a SEQUENCE of launches (chain64_run at the end of this file): one batched weight pack, then
+// the layers left to right as fused conv pairs (conv_pair64, po2q_conv_pair64.hip: the intermediate of
+// a pair stays on chip) wherever two consecutive layers have the plain form, every other layer through
+// the single-conv path with its fused epilogue, activations between launches in the workspace.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -544,6 +550,132 @@ ChainWs chain_ws(int64_t N, int64_t C, int64_t H, int64_t W, int n_layers) {
     L.total = L.scale_off + chain_align((size_t)n_layers * 4);
     return L;
 }
+
+// ---- the large C = 64 geometry: a run of launches (pairs + single convs) ----
+bool chain64_geom_ok(int64_t N, int64_t C, int64_t H, int64_t W, int n_layers) {
+    return pair64_enabled() && pair64_geom_ok(N, C, H, W) && n_layers >= 2 && n_layers <= kChainMax;
+}
+
+// Workspace: one slot per layer (a pair layer: its scale, then its pack; a single-conv layer: that
+// plan's own layout), then two activation buffers (with y: three to rotate through)
+struct Chain64Ws {
+    size_t slot, act_off, act_bytes, total;
+};
+Chain64Ws chain64_ws(int64_t N, int64_t C, int64_t H, int64_t W, int n_layers) {
+    Chain64Ws L;
+    L.slot = chain_align(std::max(kChainAlign + pair64_pack_bytes(), single_ws_max(N, C, H, W)));
+    L.act_off = L.slot * (size_t)n_layers;
+    L.act_bytes = chain_align((size_t)(N * C * H * W) * 4);
+    L.total = L.act_off + 2 * L.act_bytes;
+    return L;
+}
+
+struct Chain64Launch {
+    int l0, len;  // layers l0 .. l0 + len - 1 (len 2: a pair)
+    int out;      // buffer of a_{l0 + len}: 0 / 1 the workspace's, 2 = y
+};
+
+// Buffers for the activations the launches write: never a launch's own input, never a residual source
+// a later (or this) layer still adds, the last one y.  buf[j]: buffer of a_j (-1: x, -2: not materialised).
+bool chain64_assign(std::vector<Chain64Launch>& ls, size_t k, std::vector<int>& buf, const int* res_from, int n) {
+    if (k == ls.size()) return true;
+    Chain64Launch& c = ls[k];
+    const bool last = k + 1 == ls.size();
+    for (int b = last ? 2 : 0; b < 3; ++b) {
+        bool ok = buf[c.l0] != b;
+        for (int l = c.l0; ok && l < n; ++l) {
+            const int r = res_from ? res_from[l] : -1;
+            if (r >= 0 && r <= c.l0 && buf[r] == b) ok = false;
+        }
+        if (!ok) continue;
+        c.out = b;
+        buf[c.l0 + c.len] = b;
+        if (chain64_assign(ls, k + 1, buf, res_from, n)) return true;
+    }
+    return false;
+}
+
+int chain64_run(const float* x, const float* const* w, const float* const* bias, const float* const* post_scale,
+                const float* const* post_shift, const int* act, const int* res_from, int n, int64_t N, int64_t C,
+                int64_t H, int64_t W, int bits, int fsr, int mode, float* y, char* ws, hipStream_t s) {
+    const Chain64Ws L = chain64_ws(N, C, H, W, n);
+    ConvPlan sp;
+    if (!single_plan(sp, N, C, H, W, bits, fsr, mode)) return PO2Q_ERR_INVALID;  // (the error is set)
+    const SingleWs sw = single_ws(sp, mode);
+    if (sw.total > L.slot) {
+        set_error("po2q: chain: the single-conv plan's workspace exceeds the layer slot");
+        return PO2Q_ERR_WORKSPACE;
+    }
+    // a_j feeds a later layer's residual add: it has to exist in memory
+    std::vector<int> used((size_t)n + 1, 0);
+    for (int l = 0; l < n; ++l)
+        if (res_from && res_from[l] >= 0) used[res_from[l]] = 1;
+    auto plain = [&](int l) {
+        return !(post_scale && post_scale[l]) && !(post_shift && post_shift[l]) && !(act && act[l] != 0) &&
+               !(res_from && res_from[l] >= 0);
+    };
+    // pairs left to right wherever the pair kernel takes the form
+    std::vector<Chain64Launch> ls;
+    for (int l = 0; l < n;) {
+        const bool pair = l + 1 < n && plain(l) && plain(l + 1) && !used[l + 1];
+        ls.push_back(Chain64Launch{l, pair ? 2 : 1, 2});
+        l += pair ? 2 : 1;
+    }
+    std::vector<int> buf((size_t)n + 1, -2);
+    buf[0] = -1;
+    if (!chain64_assign(ls, 0, buf, res_from, n)) {
+        set_error("po2q: chain: no activation buffer rotation for this res_from pattern");
+        return PO2Q_ERR_INVALID;
+    }
+    auto slot = [&](int l) { return ws + (size_t)l * L.slot; };
+    auto bufp = [&](int b) -> float* {
+        return b == 2 ? y : reinterpret_cast<float*>(ws + L.act_off + (size_t)b * L.act_bytes);
+    };
+    auto actp = [&](int j) -> const float* { return j == 0 ? x : bufp(buf[j]); };
+
+    // every weight of the run: ONE batched quantize + pack launch (a single-conv layer whose plan
+    // cannot ride it stages its own weight in its conv call)
+    const ConvPlan pk = pair64_pack_plan(N, H, W);
+    std::vector<PackReq> reqs;
+    for (const Chain64Launch& c : ls)
+        for (int l = c.l0; l < c.l0 + c.len; ++l) {
+            if (c.len == 2)
+                reqs.push_back(PackReq{&pk, w[l], slot(l) + kChainAlign, reinterpret_cast<float*>(slot(l)), bits, fsr, mode});
+            else if (sw.batch)
+                reqs.push_back(PackReq{&sp, w[l], slot(l) + sw.packed_off, reinterpret_cast<float*>(slot(l) + sw.scale_off),
+                                       bits, fsr, mode});
+        }
+    if (!reqs.empty()) {
+        const hipError_t he = launch_pack_batch((int)reqs.size(), reqs.data(), s);
+        if (he != hipSuccess) {
+            set_error(std::string("po2q: chain weight pack launch: ") + hipGetErrorString(he));
+            return PO2Q_ERR_HIP;
+        }
+    }
+    for (const Chain64Launch& c : ls) {
+        const int l = c.l0;
+        const float* in = actp(l);
+        float* out = bufp(c.out);
+        if (c.len == 2) {
+            const hipError_t he = pair64_launch(
+                in, out, N, H, W, reinterpret_cast<const uint16_t*>(slot(l) + kChainAlign),
+                reinterpret_cast<const float*>(slot(l)), reinterpret_cast<const uint16_t*>(slot(l + 1) + kChainAlign),
+                reinterpret_cast<const float*>(slot(l + 1)), bias ? bias[l] : nullptr, bias ? bias[l + 1] : nullptr, s);
+            if (he != hipSuccess) {
+                set_error(std::string("po2q: chain pair launch: ") + hipGetErrorString(he));
+                return PO2Q_ERR_HIP;
+            }
+            continue;
+        }
+        const int r = res_from ? res_from[l] : -1;
+        const ConvEpi e{post_scale ? post_scale[l] : nullptr, post_shift ? post_shift[l] : nullptr,
+                        r >= 0 ? actp(r) : nullptr, act ? act[l] : 0};
+        const int st = single_run(sp, in, w[l], bias ? bias[l] : nullptr, out, bits, fsr, mode, slot(l), L.slot, s, e,
+                                  sw.batch);
+        if (st) return st;
+    }
+    return PO2Q_OK;
+}
 }  // namespace
 
 }  // namespace po2q
@@ -554,12 +686,16 @@ extern "C" {
 
 int po2q_qconv2d_chain_supported(int64_t N, int64_t C, int64_t H, int64_t W, int n_layers, int bits, int fsr,
                                  int mode) {
-    return chain_geom_ok(N, C, H, W, n_layers) && chain_mode_ok(bits, fsr, mode) ? 1 : 0;
+    return (chain_geom_ok(N, C, H, W, n_layers) || chain64_geom_ok(N, C, H, W, n_layers)) &&
+                   chain_mode_ok(bits, fsr, mode)
+               ? 1
+               : 0;
 }
 
 size_t po2q_qconv2d_chain_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int n_layers) {
-    if (!chain_geom_ok(N, C, H, W, n_layers)) return 0;
-    return chain_ws(N, C, H, W, n_layers).total;
+    if (chain_geom_ok(N, C, H, W, n_layers)) return chain_ws(N, C, H, W, n_layers).total;
+    if (chain64_geom_ok(N, C, H, W, n_layers)) return chain64_ws(N, C, H, W, n_layers).total;
+    return 0;
 }
 
 int po2q_qconv2d_chain_f32(const float* x, const float* const* w, const float* const* bias,
@@ -570,10 +706,13 @@ int po2q_qconv2d_chain_f32(const float* x, const float* const* w, const float* c
         po2q::set_error("po2q: chain does not take the lin / lin+ modes");
         return PO2Q_ERR_UNSUPPORTED;
     }
-    if (!chain_geom_ok(N, C, H, W, n_layers)) {
+    // the large C = 64 geometry: a run of pair / single-conv launches instead of the one-launch kernel
+    const bool big = !chain_geom_ok(N, C, H, W, n_layers) && chain64_geom_ok(N, C, H, W, n_layers);
+    if (!big && !chain_geom_ok(N, C, H, W, n_layers)) {
         set_error("po2q: chain needs C in {16, 32, 64}, W % 4 == 0, 1.." + std::to_string(kChainMax) +
-                  " layers and a small image: its split planes in LDS ((H + 2)(W + 2) 6C bytes <= 160 KiB) and "
-                  "at most 8 (C = 16) / 4 (C = 32, 64) 16-pixel groups per wave");
+                  " layers and either a small image (one launch): its split planes in LDS ((H + 2)(W + 2) 6C bytes "
+                  "<= 160 KiB) and at most 8 (C = 16) / 4 (C = 32, 64) 16-pixel groups per wave; or C = 64 with "
+                  "32 < W <= 64 and at least 2 layers (a run of conv-pair launches; PO2Q_PAIR64=0 turns it off)");
         return PO2Q_ERR_INVALID;
     }
     if (!chain_mode_ok(bits, fsr, mode)) {
@@ -584,9 +723,10 @@ int po2q_qconv2d_chain_f32(const float* x, const float* const* w, const float* c
         set_error("po2q: chain: null pointer");
         return PO2Q_ERR_INVALID;
     }
-    const ChainWs L = chain_ws(N, C, H, W, n_layers);
-    if (workspace_bytes < L.total) {
-        set_error("po2q: chain workspace too small (need " + std::to_string(L.total) + " bytes)");
+    const ChainWs L = big ? ChainWs{} : chain_ws(N, C, H, W, n_layers);
+    const size_t need = big ? chain64_ws(N, C, H, W, n_layers).total : L.total;
+    if (workspace_bytes < need) {
+        set_error("po2q: chain workspace too small (need " + std::to_string(need) + " bytes)");
         return PO2Q_ERR_WORKSPACE;
     }
     for (int l = 0; l < n_layers; ++l) {
@@ -619,6 +759,14 @@ int po2q_qconv2d_chain_f32(const float* x, const float* const* w, const float* c
         }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     char* ws = reinterpret_cast<char*>(workspace);
+    if (big) {
+        if (x == y) {
+            set_error("po2q: chain: y must not alias x");
+            return PO2Q_ERR_INVALID;
+        }
+        return chain64_run(x, w, bias, post_scale, post_shift, act, res_from, n_layers, N, C, H, W, bits, fsr, mode, y,
+                           ws, s);
+    }
 
     // every layer's weight: quantize + pack in ceil(n / 36) launches
     const ConvPlan plan = chain_plan(N, C, H, W);

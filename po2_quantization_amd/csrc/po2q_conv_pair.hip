@@ -1237,7 +1237,7 @@ bool pair_args_ok(int64_t N, int64_t C, int64_t H, int64_t W, int bits, int fsr,
         return false;
     }
     if (C != 16 && C != 32) {
-        po2q::set_error("po2q: pair: 16 or 32 channels only (ResNet56 stages 1 and 2)");
+        po2q::set_error("po2q: pair: 16 or 32 channels only (ResNet56 stages 1 and 2), or 64 with 32 < W <= 64");
         return false;
     }
     if (mode != PO2Q_MODE_PO2 && mode != PO2Q_MODE_PO2_PLUS) {
@@ -1295,6 +1295,11 @@ int po2q_qconv2d_pair_f32(const float* x, const float* w1, const float* w2, floa
     if (po2q::is_lin_mode(mode)) {  // the multi-layer kernels stage po2 weights in-kernel
         po2q::set_error("po2q: pair does not take the lin / lin+ modes");
         return PO2Q_ERR_UNSUPPORTED;
+    }
+    if (C == 64 && po2q::pair64_geom_ok(N, C, H, W)) {  // stage 3 @56: the role-split C = 64 pair on two batched weight packs (po2q_conv_pair64.hip)
+        const bool plain = !post_scale1 && !post_shift1 && !post_scale2 && !post_shift2 && !residual && act1 == 0 &&
+                           act2 == 0;
+        return po2q::pair64_entry(x, w1, w2, y, N, H, W, bits, fsr, mode, bias1, bias2, plain, stream);
     }
     if (!pair_args_ok(N, C, H, W, bits, fsr, mode, act1, act2)) return PO2Q_ERR_INVALID;
     if (!x || !w1 || !w2 || !y) {

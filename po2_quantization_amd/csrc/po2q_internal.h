@@ -240,6 +240,35 @@ hipError_t pairw_launch(const float* x, const float* w1, const float* w2, float*
                         const float* post_scale1, const float* post_shift1, int act1, const float* post_scale2,
                         const float* post_shift2, const float* residual, int act2, hipStream_t s);
 
+// The stage-3 conv pair (C = 64, 32 < W <= 64; po2q_conv_pair64.hip): two chained plain convs from
+// two conv_rowsk-layout weight packs (pair64_pack_plan: the geometry launch_pack_batch packs them by).
+// pair64_entry is po2q_qconv2d_pair_f32 at C = 64 (plain: no BN affine, activation or residual asked for);
+// pair64_enabled: PO2Q_PAIR64 != 0, whether the chain entry takes the geometry.
+bool pair64_enabled();
+bool pair64_geom_ok(int64_t N, int64_t C, int64_t H, int64_t W);
+size_t pair64_pack_bytes();
+ConvPlan pair64_pack_plan(int64_t N, int64_t H, int64_t W);
+hipError_t pair64_launch(const float* x, float* y, int64_t N, int64_t H, int64_t W, const uint16_t* packed1,
+                         const float* scale1, const uint16_t* packed2, const float* scale2, const float* bias1,
+                         const float* bias2, hipStream_t s);
+int pair64_entry(const float* x, const float* w1, const float* w2, float* y, int64_t N, int64_t H, int64_t W,
+                 int bits, int fsr, int mode, const float* bias1, const float* bias2, bool plain, void* stream);
+
+// The single-conv path behind the chain entry's large C = 64 geometry (po2q_capi.hip): the plan
+// po2q_qconv2d_fused_f32 would run for a 3x3 / stride-1 / pad-1 C -> C layer (tuned or heuristic), its
+// workspace layout, and its conv from a workspace (packed: the weight was packed there by a batched
+// launch; else the layer quantizes + packs its own).
+struct SingleWs {
+    size_t total, scale_off, packed_off;
+    bool batch;  // the plan's pack can ride launch_pack_batch without absmax partials
+};
+bool single_plan(ConvPlan& p, int64_t N, int64_t C, int64_t H, int64_t W, int bits, int fsr, int mode);
+SingleWs single_ws(const ConvPlan& p, int mode);
+size_t single_ws_max(int64_t N, int64_t C, int64_t H, int64_t W);  // over every plan the layer may run
+struct ConvEpi;
+int single_run(const ConvPlan& p, const float* x, const float* w, const float* bias, float* y, int bits, int fsr,
+               int mode, void* workspace, size_t workspace_bytes, hipStream_t s, const ConvEpi& e, bool packed);
+
 // fp64 / bf16 (bit patterns) PO2 / PO2+ quantizer (po2q_quant_dtypes.hip): absmax partials
 // (nparts = absmax_blocks(n) uint64 words), then the quantize pass.
 template <typename T>

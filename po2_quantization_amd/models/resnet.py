@@ -159,7 +159,10 @@ class ResNet(nn.Module):
         """One residual stage (resnet.py:131-143 builds it).  In inference at small image sizes the
         stage's identity-shortcut blocks run as ONE chain launch (po2q_qconv2d_chain_f32: every
         block's conv1 -> bn1 -> relu -> conv2 -> bn2 -> + block input -> relu, one GPU block per
-        image); its first block, when it carries the projection shortcut, runs on its own first."""
+        image); its first block, when it carries the projection shortcut, runs on its own first.
+        The chain entry also takes stage 3 at large sizes (C = 64, 32 < W <= 64): there the blocks'
+        BN / ReLU / shortcut layers run as the fused single convs they run block by block, behind
+        one batched weight pack."""
         blocks = list(layer)
         i0 = 1 if blocks and isinstance(blocks[0], BasicBlock) and blocks[0].downsample is not None else 0
         run = blocks[i0:]
