@@ -454,37 +454,43 @@ static bool plan_fallback(ConvPlan& p, bool dw3) {
     // pixel tile: NJ groups of 16 pixels per wave
     const int pix_img = p.P * p.Q;
     p.NJ = pix_img >= 256 ? 4 : (pix_img >= 128 ? 2 : 1);
-    const int slots = 64 * p.NJ;
-    // choose TQ among candidates minimising launched slots x halo overhead
-    const int cands[] = {p.Q, 64, 56, 32, 28, 16, 8};
-    double best = 1e300;
-    for (int tq : cands) {
-        if (tq <= 0 || tq > p.Q || tq > slots) continue;
-        int tp = std::max(1, std::min(p.P, slots / tq));
-        const int tilesQ = ceil_div(p.Q, tq), tilesP = ceil_div(p.P, tp);
-        const double launched = (double)tilesQ * tilesP * slots;
-        const int hh = (tp - 1) * p.sh + (p.R - 1) * p.dh + 1;
-        const int ww = (tq - 1) * p.sw + (p.S - 1) * p.dw + 1;
-        const double halo = (double)tilesQ * tilesP * hh * ww;
-        const double cost = launched * 1.0 + halo * 0.5 * p.R * p.S / 9.0;
-        if (cost < best) { best = cost; p.TQ = tq; p.TP = tp; }
-    }
-    p.tilesQ = ceil_div(p.Q, p.TQ);
-    p.tilesP = ceil_div(p.P, p.TP);
-    p.HH = (p.TP - 1) * p.sh + (p.R - 1) * p.dh + 1;
-    p.WW = (p.TQ - 1) * p.sw + (p.S - 1) * p.dw + 1;
-    p.WWp = p.WW;
-    const int plane = p.HH * p.WWp;
-    // plane stride: lanes 16..31 read channel +1; offset it by 16 banks (stride 1)
-    // or 1 bank (stride 2: lanes already spread over even banks)
-    const int want = (p.sw == 1) ? 16 : 1;
-    p.PS = plane + ((want - plane % 32) + 32) % 32;
-    // channel chunk: multiple of 4, LDS <= 64 KiB
-    const int cg4 = ceil_div(p.Cg, 4) * 4;
-    int cc = std::min(cg4, 64);
     auto lds_for = [&](int c) {
         return (size_t)(c * p.PS + p.R * p.S * (c / 4) * p.MI * 64) * sizeof(float);
     };
+    // A large kernel at a wide stride (the 7x7 / stride-2 ImageNet stem with 64 output channels): the
+    // halo of the tile chosen from the image size alone can exceed LDS even at the smallest channel
+    // chunk.  Only then the pixel tile is halved (NJ 2, then 1); a shape that fits keeps its plan.
+    for (;; p.NJ >>= 1) {
+        const int slots = 64 * p.NJ;
+        // choose TQ among candidates minimising launched slots x halo overhead
+        const int cands[] = {p.Q, 64, 56, 32, 28, 16, 8};
+        double best = 1e300;
+        for (int tq : cands) {
+            if (tq <= 0 || tq > p.Q || tq > slots) continue;
+            int tp = std::max(1, std::min(p.P, slots / tq));
+            const int tilesQ = ceil_div(p.Q, tq), tilesP = ceil_div(p.P, tp);
+            const double launched = (double)tilesQ * tilesP * slots;
+            const int hh = (tp - 1) * p.sh + (p.R - 1) * p.dh + 1;
+            const int ww = (tq - 1) * p.sw + (p.S - 1) * p.dw + 1;
+            const double halo = (double)tilesQ * tilesP * hh * ww;
+            const double cost = launched * 1.0 + halo * 0.5 * p.R * p.S / 9.0;
+            if (cost < best) { best = cost; p.TQ = tq; p.TP = tp; }
+        }
+        p.tilesQ = ceil_div(p.Q, p.TQ);
+        p.tilesP = ceil_div(p.P, p.TP);
+        p.HH = (p.TP - 1) * p.sh + (p.R - 1) * p.dh + 1;
+        p.WW = (p.TQ - 1) * p.sw + (p.S - 1) * p.dw + 1;
+        p.WWp = p.WW;
+        const int plane = p.HH * p.WWp;
+        // plane stride: lanes 16..31 read channel +1; offset it by 16 banks (stride 1)
+        // or 1 bank (stride 2: lanes already spread over even banks)
+        const int want = (p.sw == 1) ? 16 : 1;
+        p.PS = plane + ((want - plane % 32) + 32) % 32;
+        if (lds_for(4) <= 64 * 1024 || p.NJ == 1) break;
+    }
+    // channel chunk: multiple of 4, LDS <= 64 KiB
+    const int cg4 = ceil_div(p.Cg, 4) * 4;
+    int cc = std::min(cg4, 64);
     while (cc > 4 && lds_for(cc) > 64 * 1024) cc -= 4;
     if (lds_for(cc) > 64 * 1024) {
         set_error("po2q: conv tile does not fit in LDS (kernel too large)");

@@ -12,6 +12,7 @@ from oracle import oracle as O
 from po2_quantization_amd import _lib
 from po2_quantization_amd.models.quantized_conv import QuantizedConv2d
 from po2_quantization_amd.utils.quantizers import quantizer_dict
+from tests._nonfinite import nonfinite_input as _nonfinite_input, same_nonfinite as _same_nonfinite
 from tests._util import CONV_TOL, load_json, load_npz, normwise_err
 
 pytestmark = pytest.mark.gpu
@@ -427,22 +428,6 @@ def test_small_image_kernel_every_plan_vs_oracle(shape, monkeypatch):
 
 NONFINITE_SHAPES = [(2, 16, 12, 224, 16, 3, 1, 1), (2, 32, 10, 112, 32, 3, 1, 1), (2, 64, 9, 56, 64, 3, 1, 1),
                     (2, 16, 11, 64, 32, 3, 2, 1), (2, 32, 8, 32, 64, 1, 2, 0), (2, 24, 6, 6, 144, 1, 1, 0)]
-
-
-def _nonfinite_input(N, C, H, W, seed):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(N, C, H, W, generator=g)
-    flat = x.view(-1)
-    idx = torch.randperm(flat.numel(), generator=g)[:6]
-    sig = torch.tensor([0x7F800001], dtype=torch.int32).view(torch.float32)  # signaling NaN, low payload only
-    for v, i in zip((float("inf"), float("-inf"), float("nan"), float("inf"), sig.item(), float("-inf")), idx):
-        flat[i] = v
-    return x
-
-
-def _same_nonfinite(y, ref):
-    return (torch.equal(torch.isnan(y), torch.isnan(ref)) and torch.equal(torch.isposinf(y), torch.isposinf(ref))
-            and torch.equal(torch.isneginf(y), torch.isneginf(ref)))
 
 
 def _oracle_ref(x, w, st, pad, mode="po2"):
