@@ -153,8 +153,9 @@ int po2q_qconv2d_f32(const float* x, const float* w, const float* bias, float* y
  * PO2Q_ERR_UNSUPPORTED.  Arguments are validated as by po2q_qconv2d_f32 (same messages).
  * At most two launches precede the conv (max|w|, then quantize + pack; mode none: the pack alone).
  * The tile comes from a heuristic; po2q_qconv2d_bf16_describe names the kernel and its tile
- * ("kind=bf16x1 ..." / "kind=dw_bf16 ...").  po2q_qconv2d_bf16_workspace_bytes returns 0 (and sets
- * the error) for arguments the entry rejects.
+ * ("kind=bf16x1 ..." / "kind=dw_bf16 ...", and with the row kernels switched on, below,
+ * "kind=bf16_rows C=.. RB=.. bands=.. groups=.. ring=.. lds=.. blocks=.." for the layers they take).
+ * po2q_qconv2d_bf16_workspace_bytes returns 0 (and sets the error) for arguments the entry rejects.
  */
 size_t po2q_qconv2d_bf16_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W,
                                          int64_t K, int64_t R, int64_t S,
@@ -272,6 +273,26 @@ int po2q_qconv2d_packed_bf16(const uint16_t* x, const uint16_t* bias, uint16_t* 
                              int bits, int fsr, int mode,
                              const float* post_scale, const float* post_shift, const uint16_t* residual, int act,
                              const void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Opt-in row-streaming kernel of the bf16 conv entries (conv_b16_rows, "kind=bf16_rows").  With the
+ * switch on, every bf16 entry above plans it for the layers it takes: groups 1, a 3x3 kernel,
+ * stride 1, pad 1, dilation 1, C == K in {16, 32}, W even and <= 256.  Every other layer, and every
+ * layer while the switch is off (the default), keeps the tile / depthwise kernel: description,
+ * workspace size and output bits unchanged.  The arithmetic is the tile kernel's (Q(w) from the
+ * same quantize body, one v_mfma_f32_16x16x32_bf16 per k-step, fp32 accumulation, one rounding);
+ * only the accumulation order differs.
+ * po2q_bf16_set_row_kernels(on) sets the switch (on != 0: on) and returns the previous value (0 / 1);
+ * po2q_bf16_row_kernels() returns the current one.  The state is process-wide and atomic; its
+ * initial value is the environment variable PO2Q_B16_ROWS (unset or 0: off), read once.
+ * The plan is made anew by every call, so po2q_qconv2d_bf16_workspace_bytes, _describe and the
+ * entries follow the switch at once.  A workspace filled by po2q_qconv2d_bf16_pack_batch belongs to
+ * the setting it was packed under, as it belongs to its geometry: the two kernels read different
+ * weight layouts.  po2q_qconv2d_packed_bf16 checks the size only (PO2Q_ERR_WORKSPACE when the
+ * current plan needs more than it is given).
+ */
+int po2q_bf16_set_row_kernels(int on);
+int po2q_bf16_row_kernels(void);
 
 /*
  * Kernel autotuning, the counterpart of the reference's

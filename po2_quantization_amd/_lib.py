@@ -13,6 +13,7 @@ torch fallback for them.  bf16 HIP tensors have the forward-only qconv2d_bf16 (p
 (the reference preserves dtype); other inputs (CPU tensors, fp16, ...) take
 restated_quantize, the reference formula written as torch ops in the input's dtype and device.
 """
+import contextlib
 import ctypes
 import os
 
@@ -76,6 +77,8 @@ EXPORTS = (
     "po2q_qconv2d_bf16_describe",
     "po2q_qconv2d_bf16_pack_batch",
     "po2q_qconv2d_packed_bf16",
+    "po2q_bf16_set_row_kernels",
+    "po2q_bf16_row_kernels",
 )
 
 # Kernel autotuning on the first call per conv problem, the counterpart of
@@ -215,6 +218,10 @@ def load():
     L.po2q_qconv2d_wgrad_describe.argtypes = [i64] * 14 + [ctypes.c_char_p, sz]
     L.po2q_qconv2d_packed_bf16.restype = i32
     L.po2q_qconv2d_packed_bf16.argtypes = [p, p, p] + [i64] * 14 + [i32, i32, i32, p, p, p, i32, p, sz, p]
+    L.po2q_bf16_set_row_kernels.restype = i32
+    L.po2q_bf16_set_row_kernels.argtypes = [i32]
+    L.po2q_bf16_row_kernels.restype = i32
+    L.po2q_bf16_row_kernels.argtypes = []
     _lib = L
     return L
 
@@ -541,6 +548,29 @@ def describe_bf16(N, C, H, W, K, R, S, stride=1, padding=0, dilation=1, groups=1
     _check(L.po2q_qconv2d_bf16_describe(N, C, H, W, K, R, S, *_pair(stride), *_pair(padding), *_pair(dilation),
                                         int(groups), int(bits), int(fsr), MODES[mode], buf, 512))
     return buf.value.decode()
+
+
+def set_bf16_row_kernels(on):
+    """Switch the bf16 entries' opt-in row-streaming kernel (po2q_bf16_set_row_kernels: 3x3 / stride 1 /
+    pad 1 layers with C == K in {16, 32}, W even and <= 256; "kind=bf16_rows") on or off for the whole
+    process; returns the previous setting.  Off by default (PO2Q_B16_ROWS gives the initial value).  A
+    workspace pack_batch_bf16 filled belongs to the setting it was packed under."""
+    return bool(load().po2q_bf16_set_row_kernels(1 if on else 0))
+
+
+def bf16_row_kernels():
+    """Whether the bf16 entries plan the row-streaming kernel for the layers it takes."""
+    return bool(load().po2q_bf16_row_kernels())
+
+
+@contextlib.contextmanager
+def bf16_rows(on=True):
+    """set_bf16_row_kernels(on) for the body; the previous setting is restored on the way out."""
+    prev = set_bf16_row_kernels(on)
+    try:
+        yield
+    finally:
+        set_bf16_row_kernels(prev)
 
 
 def qconv2d_fused(x, w, bias=None, stride=1, padding=0, dilation=1, groups=1, bits=4, mode="po2", fsr=1,

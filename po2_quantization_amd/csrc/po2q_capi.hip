@@ -749,6 +749,10 @@ int po2q_qconv2d_bf16_describe(int64_t N, int64_t C, int64_t H, int64_t W, int64
     return PO2Q_OK;
 }
 
+int po2q_bf16_set_row_kernels(int on) { return b16_rows_set(on); }
+
+int po2q_bf16_row_kernels(void) { return b16_rows_get(); }
+
 }  // extern "C"
 
 // ------------------------------------------------------------------ plan handles --

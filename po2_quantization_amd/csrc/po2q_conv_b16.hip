@@ -405,7 +405,9 @@ __global__ __launch_bounds__(kThreads) void absmax_b16(const uint16_t* __restric
 
 struct PackB16Args {
     int C, K, taps, CC, NT, ksteps, nchunks, kblocks;
-    int dense;       // 1: MFMA B fragments [kb][chunk][ks][nt][lane][8]; 0: plain copy [n]
+    int dense;       // 1: MFMA B fragments [kb][chunk][ks][nt][lane][8]; 0: plain copy [n];
+                     // 2: the row kernel's fragments [tap row][ks][nt][lane][8] (3x3, C = CC: taps per k-step
+                     //    run over one tap row's 3 columns, po2q_conv_b16r.hip)
     int64_t n;       // weight elements
     int64_t nfrag;   // dense: uint4 fragments
     int quant, mode, lo, hi;  // quant 0: the weight as given (mode none)
@@ -441,9 +443,11 @@ __device__ __forceinline__ void pack_b16_body(const uint16_t* __restrict__ w, co
         const int chunk = (int)(r % a.nchunks);
         const int kb = (int)(r / a.nchunks);
         const int oi = ks * 4 + (lane >> 4);
-        const int t = oi / oct, oc = oi % oct;
+        int t = oi / oct;
+        const int oc = oi % oct;
+        if (a.dense == 2) t = t < 3 ? chunk * 3 + t : a.taps;  // `chunk` counts the tap row here; column 3 is padding
         const int k = kb * 16 * a.NT + nt * 16 + (lane & 15);
-        const int c0 = chunk * a.CC + oc * 8;
+        const int c0 = (a.dense == 2 ? 0 : chunk * a.CC) + oc * 8;
         uint32_t q[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -568,6 +572,7 @@ int b16_plan(ConvPlan& p) {
         p.packed_floats = ((int64_t)p.K * p.taps * 2 + 3) / 4;  // Q(w) [C][R*S] bf16
         return 0;
     }
+    if (b16_rows_plan(p)) return 0;  // opt-in (po2q_bf16_set_row_kernels) and eligible
     p.kind = KIND_BF16X1;
     p.CC = (p.taps == 1 && p.C > 16) ? 32 : 16;
     const int OCT = p.CC / 8;
@@ -632,7 +637,9 @@ size_t b16_workspace_bytes(const ConvPlan& p) {
 }
 
 void b16_describe(const ConvPlan& p, char* buf, size_t len) {
-    if (p.kind == KIND_DW_BF16)
+    if (p.kind == KIND_BF16_ROWS)
+        b16_rows_describe(p, buf, len);
+    else if (p.kind == KIND_DW_BF16)
         snprintf(buf, len, "kind=dw_bf16 taps=%dx%d blocks=%lld", p.R, p.S, (long long)p.blocks);
     else
         snprintf(buf, len,
@@ -654,7 +661,8 @@ PackB16Args b16_pack_args(const ConvPlan& p, int bits, int fsr, int mode) {
     PackB16Args pa;
     pa.C = p.Cg; pa.K = p.K; pa.taps = p.taps; pa.CC = p.CC; pa.NT = p.NT; pa.ksteps = p.steps;
     pa.nchunks = p.nchunks; pa.kblocks = p.kblocks;
-    pa.dense = p.kind == KIND_BF16X1 ? 1 : 0;
+    pa.dense = p.kind == KIND_BF16X1 ? 1 : (p.kind == KIND_BF16_ROWS ? 2 : 0);
+    if (pa.dense == 2) pa.nchunks = 3;  // the fragment index's chunk field is the tap row
     pa.n = nw;
     pa.nfrag = pa.dense ? p.packed_floats / 4 : 0;
     pa.quant = mode != 0 ? 1 : 0;
@@ -720,6 +728,7 @@ hipError_t b16_run(const ConvPlan& p, const uint16_t* x, const uint16_t* w, cons
 hipError_t b16_run_packed(const ConvPlan& p, const uint16_t* x, const uint16_t* bias, uint16_t* y,
                           const void* workspace, hipStream_t s, const B16Epi& epi) {
     const uint16_t* packed = b16_packed_ptr(const_cast<void*>(workspace));
+    if (p.kind == KIND_BF16_ROWS) return b16_rows_launch(p, x, packed, bias, y, s, epi);
     if (p.kind == KIND_DW_BF16) {
         DwB16Args d;
         d.C = p.C; d.H = p.H; d.W = p.W; d.P = p.P; d.Q = p.Q; d.R = p.R; d.S = p.S;

@@ -46,7 +46,8 @@ enum ConvKind {
     KIND_PW_F32 = 7,      // unquantized 1x1 convs, fp32 MFMA GEMM (po2q_conv_f32s.hip)
     KIND_BF16X3_IMG = 8,  // 3x3 / stride 1, small images: the block's rows resident in LDS (po2q_conv_img.hip)
     KIND_BF16X1 = 9,      // bf16 in / out, one bf16 MFMA pass (po2q_conv_b16.hip; po2q_qconv2d_bf16 only)
-    KIND_DW_BF16 = 10     // bf16 in / out depthwise, direct (po2q_conv_b16.hip; po2q_qconv2d_bf16 only)
+    KIND_DW_BF16 = 10,    // bf16 in / out depthwise, direct (po2q_conv_b16.hip; po2q_qconv2d_bf16 only)
+    KIND_BF16_ROWS = 11   // bf16 in / out, row-streaming 3x3 / stride 1, C = K in {16, 32} (po2q_conv_b16r.hip; opt-in)
 };
 
 // Every kind whose weight is packed as exact bf16 fragments (+-2^e for po2 / po2+, delta_c * q for
@@ -305,6 +306,21 @@ struct B16PackReq {
 hipError_t b16_pack_batch(int n, const B16PackReq* reqs, hipStream_t s);
 hipError_t b16_run_packed(const ConvPlan& p, const uint16_t* x, const uint16_t* bias, uint16_t* y,
                           const void* workspace, hipStream_t s, const B16Epi& e = B16Epi{});
+
+// Row-streaming bf16 kernel (po2q_conv_b16r.hip, kind KIND_BF16_ROWS).  The switch is process-wide and
+// atomic (initial value: PO2Q_B16_ROWS, read once); b16_rows_set returns the previous value.
+// b16_rows_plan fills the plan of a validated geometry and returns true only when the switch is on and
+// the geometry is eligible (3x3, stride 1, pad 1, dilation 1, groups 1, C = K in {16, 32}, W even and
+// <= b16_rows_wmax()); b16_plan asks it first.  Its weight pack is pack_b16's row layout
+// [tap row][k-step][nt][lane][8]; plan fields: TP = RB, tilesP = bands, tilesQ = 16-column groups,
+// NJ = groups per wave, pd = LDS planes.
+int b16_rows_get();
+int b16_rows_set(int on);
+int b16_rows_wmax();
+bool b16_rows_plan(ConvPlan& p);
+void b16_rows_describe(const ConvPlan& p, char* buf, size_t len);
+hipError_t b16_rows_launch(const ConvPlan& p, const uint16_t* x, const uint16_t* packed, const uint16_t* bias,
+                           uint16_t* y, hipStream_t s, const B16Epi& e);
 
 // lin / lin+ quantizer (po2q_lin.hip): w, out [d0, d1, rs = d2*d3], one block per d1 channel
 hipError_t launch_quantize_lin(const float* w, float* out, int d0, int d1, int rs, int bits, int num_iters, int plus,

@@ -388,16 +388,18 @@ def batched_packs(model, x):
     if rec is None:  # keyed by the model object itself: DataParallel replicas (shallow __dict__ copies) get their own
         rec = _RECORDS[model] = {}
     # the keys carry the input dtype and BF16_FUSED_EPILOGUE: a model moved between .float() and
-    # .bfloat16() at one input shape never reads the other dtype's record
+    # .bfloat16() at one input shape never reads the other dtype's record.  They carry the bf16 row-kernel
+    # switch too: a pack belongs to the setting it was made under (the two kernels' weight layouts differ)
+    rows = _lib.bf16_row_kernels()
     if x.dtype == torch.bfloat16:
-        key = (tuple(x.shape), x.device, x.dtype, BF16_FUSED_EPILOGUE, INFERENCE_FUSION)
+        key = (tuple(x.shape), x.device, x.dtype, BF16_FUSED_EPILOGUE, INFERENCE_FUSION, rows)
         sess = _ForwardPacksBf16(model, rec.get(key))
     else:
         # the record holds which layers read a packed weight and with which plan; it depends on the
         # layers' quantizer settings and precision as much as on the input shape
         confs = tuple((m.bits, native_mode(m.quantize_fn), m.precision) for m in model.modules()
                       if isinstance(m, QuantizedConv2d))
-        key = (tuple(x.shape), x.device, x.dtype, BF16_FUSED_EPILOGUE, INFERENCE_FUSION, IR_FUSION, confs)
+        key = (tuple(x.shape), x.device, x.dtype, BF16_FUSED_EPILOGUE, INFERENCE_FUSION, IR_FUSION, confs, rows)
         sess = _ForwardPacks(model, rec.get(key))
     _tls.packs = sess
     try:
