@@ -154,7 +154,8 @@ int po2q_qconv2d_f32(const float* x, const float* w, const float* bias, float* y
  * At most two launches precede the conv (max|w|, then quantize + pack; mode none: the pack alone).
  * The tile comes from a heuristic; po2q_qconv2d_bf16_describe names the kernel and its tile
  * ("kind=bf16x1 ..." / "kind=dw_bf16 ...", and with the row kernels switched on, below,
- * "kind=bf16_rows C=.. RB=.. bands=.. groups=.. ring=.. lds=.. blocks=.." for the layers they take).
+ * "kind=bf16_rows C=.. RB=.. bands=.. groups=.. ring=.. lds=.. blocks=.." or "kind=bf16_rowsk ..." for the
+ * layers they take).
  * po2q_qconv2d_bf16_workspace_bytes returns 0 (and sets the error) for arguments the entry rejects.
  */
 size_t po2q_qconv2d_bf16_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W,
@@ -293,6 +294,24 @@ int po2q_qconv2d_packed_bf16(const uint16_t* x, const uint16_t* bias, uint16_t* 
  */
 int po2q_bf16_set_row_kernels(int on);
 int po2q_bf16_row_kernels(void);
+
+/*
+ * Opt-in row-streaming kernel for the C == K == 64 layers (conv_b16_rowsk, "kind=bf16_rowsk C=64 RB=..
+ * bands=.. groups=.. GW=.. ring=.. lds=.. blocks=.."), behind a switch of its own.  With it on, every
+ * bf16 entry above plans it for: groups 1, a 3x3 kernel, stride 1, pad 1, dilation 1, C == K == 64, W
+ * even and <= 64.  Every other layer, and every layer while this switch is off (the default), is
+ * planned exactly as without it, whatever po2q_bf16_row_kernels() says: description, workspace size
+ * and output bits unchanged.  The two switches neither read nor write each other.  The arithmetic
+ * is the tile kernel's (Q(w) from the same quantize body, one v_mfma_f32_16x16x32_bf16 per k-step,
+ * fp32 accumulation, one rounding); only the accumulation order differs.
+ * po2q_bf16_set_rowsk_kernels(on) sets the switch (on != 0: on) and returns the previous value
+ * (0 / 1); po2q_bf16_rowsk_kernels() returns the current one.  The state is process-wide and atomic;
+ * its initial value is the environment variable PO2Q_B16_ROWSK (unset or 0: off), read once.
+ * As above, the plan is made anew by every call, and a workspace filled by
+ * po2q_qconv2d_bf16_pack_batch belongs to the pair of settings it was packed under.
+ */
+int po2q_bf16_set_rowsk_kernels(int on);
+int po2q_bf16_rowsk_kernels(void);
 
 /*
  * Kernel autotuning, the counterpart of the reference's

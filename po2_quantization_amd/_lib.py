@@ -79,6 +79,8 @@ EXPORTS = (
     "po2q_qconv2d_packed_bf16",
     "po2q_bf16_set_row_kernels",
     "po2q_bf16_row_kernels",
+    "po2q_bf16_set_rowsk_kernels",
+    "po2q_bf16_rowsk_kernels",
 )
 
 # Kernel autotuning on the first call per conv problem, the counterpart of
@@ -222,6 +224,10 @@ def load():
     L.po2q_bf16_set_row_kernels.argtypes = [i32]
     L.po2q_bf16_row_kernels.restype = i32
     L.po2q_bf16_row_kernels.argtypes = []
+    L.po2q_bf16_set_rowsk_kernels.restype = i32
+    L.po2q_bf16_set_rowsk_kernels.argtypes = [i32]
+    L.po2q_bf16_rowsk_kernels.restype = i32
+    L.po2q_bf16_rowsk_kernels.argtypes = []
     _lib = L
     return L
 
@@ -571,6 +577,29 @@ def bf16_rows(on=True):
         yield
     finally:
         set_bf16_row_kernels(prev)
+
+
+def set_bf16_rowsk_kernels(on):
+    """Switch the bf16 entries' opt-in row-streaming kernel for C == K == 64 (po2q_bf16_set_rowsk_kernels:
+    3x3 / stride 1 / pad 1 layers, W even and <= 64; "kind=bf16_rowsk") on or off for the whole process;
+    returns the previous setting.  Off by default (PO2Q_B16_ROWSK gives the initial value) and independent
+    of set_bf16_row_kernels.  A workspace pack_batch_bf16 filled belongs to the settings it was packed under."""
+    return bool(load().po2q_bf16_set_rowsk_kernels(1 if on else 0))
+
+
+def bf16_rowsk_kernels():
+    """Whether the bf16 entries plan the C == K == 64 row-streaming kernel for the layers it takes."""
+    return bool(load().po2q_bf16_rowsk_kernels())
+
+
+@contextlib.contextmanager
+def bf16_rowsk(on=True):
+    """set_bf16_rowsk_kernels(on) for the body; the previous setting is restored on the way out."""
+    prev = set_bf16_rowsk_kernels(on)
+    try:
+        yield
+    finally:
+        set_bf16_rowsk_kernels(prev)
 
 
 def qconv2d_fused(x, w, bias=None, stride=1, padding=0, dilation=1, groups=1, bits=4, mode="po2", fsr=1,

@@ -753,6 +753,10 @@ int po2q_bf16_set_row_kernels(int on) { return b16_rows_set(on); }
 
 int po2q_bf16_row_kernels(void) { return b16_rows_get(); }
 
+int po2q_bf16_set_rowsk_kernels(int on) { return b16_rowsk_set(on); }
+
+int po2q_bf16_rowsk_kernels(void) { return b16_rowsk_get(); }
+
 }  // extern "C"
 
 // ------------------------------------------------------------------ plan handles --

@@ -406,8 +406,9 @@ __global__ __launch_bounds__(kThreads) void absmax_b16(const uint16_t* __restric
 struct PackB16Args {
     int C, K, taps, CC, NT, ksteps, nchunks, kblocks;
     int dense;       // 1: MFMA B fragments [kb][chunk][ks][nt][lane][8]; 0: plain copy [n];
-                     // 2: the row kernel's fragments [tap row][ks][nt][lane][8] (3x3, C = CC: taps per k-step
-                     //    run over one tap row's 3 columns, po2q_conv_b16r.hip)
+                     // 2: the row kernels' fragments [kb][tap row][ks][nt][lane][8] (3x3, C = CC: a k-step's
+                     //    octets run over one tap row's 3 columns, channel-minor; po2q_conv_b16r.hip: kblocks 1,
+                     //    po2q_conv_b16rk.hip: NT 1 and one k-block per 16-channel tile, C = 64 without padding)
     int64_t n;       // weight elements
     int64_t nfrag;   // dense: uint4 fragments
     int quant, mode, lo, hi;  // quant 0: the weight as given (mode none)
@@ -572,7 +573,8 @@ int b16_plan(ConvPlan& p) {
         p.packed_floats = ((int64_t)p.K * p.taps * 2 + 3) / 4;  // Q(w) [C][R*S] bf16
         return 0;
     }
-    if (b16_rows_plan(p)) return 0;  // opt-in (po2q_bf16_set_row_kernels) and eligible
+    if (b16_rowsk_plan(p)) return 0;  // opt-in (po2q_bf16_set_rowsk_kernels) and eligible
+    if (b16_rows_plan(p)) return 0;   // opt-in (po2q_bf16_set_row_kernels) and eligible
     p.kind = KIND_BF16X1;
     p.CC = (p.taps == 1 && p.C > 16) ? 32 : 16;
     const int OCT = p.CC / 8;
@@ -637,7 +639,9 @@ size_t b16_workspace_bytes(const ConvPlan& p) {
 }
 
 void b16_describe(const ConvPlan& p, char* buf, size_t len) {
-    if (p.kind == KIND_BF16_ROWS)
+    if (p.kind == KIND_BF16_ROWSK)
+        b16_rowsk_describe(p, buf, len);
+    else if (p.kind == KIND_BF16_ROWS)
         b16_rows_describe(p, buf, len);
     else if (p.kind == KIND_DW_BF16)
         snprintf(buf, len, "kind=dw_bf16 taps=%dx%d blocks=%lld", p.R, p.S, (long long)p.blocks);
@@ -661,8 +665,13 @@ PackB16Args b16_pack_args(const ConvPlan& p, int bits, int fsr, int mode) {
     PackB16Args pa;
     pa.C = p.Cg; pa.K = p.K; pa.taps = p.taps; pa.CC = p.CC; pa.NT = p.NT; pa.ksteps = p.steps;
     pa.nchunks = p.nchunks; pa.kblocks = p.kblocks;
-    pa.dense = p.kind == KIND_BF16X1 ? 1 : (p.kind == KIND_BF16_ROWS ? 2 : 0);
+    const bool rows = p.kind == KIND_BF16_ROWS || p.kind == KIND_BF16_ROWSK;
+    pa.dense = p.kind == KIND_BF16X1 ? 1 : (rows ? 2 : 0);
     if (pa.dense == 2) pa.nchunks = 3;  // the fragment index's chunk field is the tap row
+    if (p.kind == KIND_BF16_ROWSK) {    // [channel tile][tap row][k-step][lane][8]: the k-block field is the tile
+        pa.NT = 1;
+        pa.kblocks = p.NT;
+    }
     pa.n = nw;
     pa.nfrag = pa.dense ? p.packed_floats / 4 : 0;
     pa.quant = mode != 0 ? 1 : 0;
@@ -728,6 +737,7 @@ hipError_t b16_run(const ConvPlan& p, const uint16_t* x, const uint16_t* w, cons
 hipError_t b16_run_packed(const ConvPlan& p, const uint16_t* x, const uint16_t* bias, uint16_t* y,
                           const void* workspace, hipStream_t s, const B16Epi& epi) {
     const uint16_t* packed = b16_packed_ptr(const_cast<void*>(workspace));
+    if (p.kind == KIND_BF16_ROWSK) return b16_rowsk_launch(p, x, packed, bias, y, s, epi);
     if (p.kind == KIND_BF16_ROWS) return b16_rows_launch(p, x, packed, bias, y, s, epi);
     if (p.kind == KIND_DW_BF16) {
         DwB16Args d;

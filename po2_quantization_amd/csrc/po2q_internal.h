@@ -47,7 +47,8 @@ enum ConvKind {
     KIND_BF16X3_IMG = 8,  // 3x3 / stride 1, small images: the block's rows resident in LDS (po2q_conv_img.hip)
     KIND_BF16X1 = 9,      // bf16 in / out, one bf16 MFMA pass (po2q_conv_b16.hip; po2q_qconv2d_bf16 only)
     KIND_DW_BF16 = 10,    // bf16 in / out depthwise, direct (po2q_conv_b16.hip; po2q_qconv2d_bf16 only)
-    KIND_BF16_ROWS = 11   // bf16 in / out, row-streaming 3x3 / stride 1, C = K in {16, 32} (po2q_conv_b16r.hip; opt-in)
+    KIND_BF16_ROWS = 11,  // bf16 in / out, row-streaming 3x3 / stride 1, C = K in {16, 32} (po2q_conv_b16r.hip; opt-in)
+    KIND_BF16_ROWSK = 12  // the same with C = K = 64, output channels split over the waves (po2q_conv_b16rk.hip; opt-in)
 };
 
 // Every kind whose weight is packed as exact bf16 fragments (+-2^e for po2 / po2+, delta_c * q for
@@ -321,6 +322,20 @@ bool b16_rows_plan(ConvPlan& p);
 void b16_rows_describe(const ConvPlan& p, char* buf, size_t len);
 hipError_t b16_rows_launch(const ConvPlan& p, const uint16_t* x, const uint16_t* packed, const uint16_t* bias,
                            uint16_t* y, hipStream_t s, const B16Epi& e);
+
+// Its C = K = 64 member (po2q_conv_b16rk.hip, kind KIND_BF16_ROWSK), behind a switch of its own
+// (initial value: PO2Q_B16_ROWSK, read once) that neither reads nor writes the one above.
+// b16_rowsk_plan returns true only when its switch is on and the geometry is eligible (3x3, stride 1,
+// pad 1, dilation 1, groups 1, C = K = 64, W even and <= b16_rowsk_wmax()); b16_plan asks it before
+// b16_rows_plan.  Weight pack: pack_b16's row layout per channel tile, [channel tile][tap row][k-step]
+// [lane][8]; plan fields as for KIND_BF16_ROWS (NJ = groups per wave = every group of the row).
+int b16_rowsk_get();
+int b16_rowsk_set(int on);
+int b16_rowsk_wmax();
+bool b16_rowsk_plan(ConvPlan& p);
+void b16_rowsk_describe(const ConvPlan& p, char* buf, size_t len);
+hipError_t b16_rowsk_launch(const ConvPlan& p, const uint16_t* x, const uint16_t* packed, const uint16_t* bias,
+                            uint16_t* y, hipStream_t s, const B16Epi& e);
 
 // lin / lin+ quantizer (po2q_lin.hip): w, out [d0, d1, rs = d2*d3], one block per d1 channel
 hipError_t launch_quantize_lin(const float* w, float* out, int d0, int d1, int rs, int bits, int num_iters, int plus,

@@ -376,6 +376,21 @@ class _ForwardPacksBf16:
 _RECORDS = weakref.WeakKeyDictionary()
 
 
+def _record_key(model, x):
+    """The key a forward's pack record is filed under.  It carries the input dtype and BF16_FUSED_EPILOGUE:
+    a model moved between .float() and .bfloat16() at one input shape never reads the other dtype's record.
+    It carries both bf16 row-kernel switches too: a pack belongs to the settings it was made under (the
+    kernels' weight layouts differ)."""
+    rows = (_lib.bf16_row_kernels(), _lib.bf16_rowsk_kernels())
+    if x.dtype == torch.bfloat16:
+        return (tuple(x.shape), x.device, x.dtype, BF16_FUSED_EPILOGUE, INFERENCE_FUSION, rows)
+    # the record holds which layers read a packed weight and with which plan; it depends on the
+    # layers' quantizer settings and precision as much as on the input shape
+    confs = tuple((m.bits, native_mode(m.quantize_fn), m.precision) for m in model.modules()
+                  if isinstance(m, QuantizedConv2d))
+    return (tuple(x.shape), x.device, x.dtype, BF16_FUSED_EPILOGUE, INFERENCE_FUSION, IR_FUSION, confs, rows)
+
+
 @contextlib.contextmanager
 def batched_packs(model, x):
     """Run a model's eval forward with its single-conv layers' weight packs batched (BATCHED_PACKS)."""
@@ -387,19 +402,10 @@ def batched_packs(model, x):
     rec = _RECORDS.get(model)
     if rec is None:  # keyed by the model object itself: DataParallel replicas (shallow __dict__ copies) get their own
         rec = _RECORDS[model] = {}
-    # the keys carry the input dtype and BF16_FUSED_EPILOGUE: a model moved between .float() and
-    # .bfloat16() at one input shape never reads the other dtype's record.  They carry the bf16 row-kernel
-    # switch too: a pack belongs to the setting it was made under (the two kernels' weight layouts differ)
-    rows = _lib.bf16_row_kernels()
+    key = _record_key(model, x)
     if x.dtype == torch.bfloat16:
-        key = (tuple(x.shape), x.device, x.dtype, BF16_FUSED_EPILOGUE, INFERENCE_FUSION, rows)
         sess = _ForwardPacksBf16(model, rec.get(key))
     else:
-        # the record holds which layers read a packed weight and with which plan; it depends on the
-        # layers' quantizer settings and precision as much as on the input shape
-        confs = tuple((m.bits, native_mode(m.quantize_fn), m.precision) for m in model.modules()
-                      if isinstance(m, QuantizedConv2d))
-        key = (tuple(x.shape), x.device, x.dtype, BF16_FUSED_EPILOGUE, INFERENCE_FUSION, IR_FUSION, confs, rows)
         sess = _ForwardPacks(model, rec.get(key))
     _tls.packs = sess
     try:

@@ -149,11 +149,13 @@ def tensor_loader(data_file: str, batch_size: int):
 
 def main(model_type: str, dataset: str, data_file: str, batch_size: int = 128, train_dir: str = "./train",
          results_dir: str = "./results", skip_qat: bool = False, dtype: str = "fp32",
-         bf16_fused_epilogue: bool = False, bf16_row_kernels: bool = False) -> None:
+         bf16_fused_epilogue: bool = False, bf16_row_kernels: bool = False,
+         bf16_rowsk_kernels: bool = False) -> None:
     """test.py:58-164 with the evaluation set from data_file."""
     assert dtype in DTYPES, "invalid dtype"
     assert not bf16_fused_epilogue or dtype == "bf16", "--bf16-fused-epilogue needs --dtype bf16"
     assert not bf16_row_kernels or dtype == "bf16", "--bf16-row-kernels needs --dtype bf16"
+    assert not bf16_rowsk_kernels or dtype == "bf16", "--bf16-rowsk-kernels needs --dtype bf16"
     assert torch.cuda.is_available(), "invalid hardware"
     assert model_type in ["resnet20", "resnet32", "resnet44", "resnet56", "mobilenet", "mobilevit"], \
         "invalid model type"
@@ -169,6 +171,7 @@ def main(model_type: str, dataset: str, data_file: str, batch_size: int = 128, t
     saved = quantized_conv.BF16_FUSED_EPILOGUE
     quantized_conv.BF16_FUSED_EPILOGUE = bool(bf16_fused_epilogue)  # for this run
     saved_rows = _lib.set_bf16_row_kernels(bool(bf16_row_kernels))  # for this run
+    saved_rowsk = _lib.set_bf16_rowsk_kernels(bool(bf16_rowsk_kernels))  # for this run
     try:
         for seed_dir in sorted(glob.glob(f"{work_dir}/*")):
             seed = os.path.basename(seed_dir)
@@ -178,6 +181,7 @@ def main(model_type: str, dataset: str, data_file: str, batch_size: int = 128, t
     finally:
         quantized_conv.BF16_FUSED_EPILOGUE = saved
         _lib.set_bf16_row_kernels(saved_rows)
+        _lib.set_bf16_rowsk_kernels(saved_rowsk)
 
 
 def arg_parser():
@@ -199,10 +203,13 @@ def arg_parser():
     ap.add_argument("--bf16-row-kernels", action="store_true",
                     help="with --dtype bf16: the row-streaming conv kernel for the 3x3 stride-1 C = K = 16 / 32 "
                          "layers (_lib.set_bf16_row_kernels), for this run")
+    ap.add_argument("--bf16-rowsk-kernels", action="store_true",
+                    help="with --dtype bf16: the row-streaming conv kernel for the 3x3 stride-1 C = K = 64 layers "
+                         "(_lib.set_bf16_rowsk_kernels), for this run")
     return ap
 
 
 if __name__ == "__main__":
     a = arg_parser().parse_args()
     main(a.model_type, a.dataset, a.data_file, a.batch_size, a.train_dir, a.results_dir, a.skip_qat, a.dtype,
-         a.bf16_fused_epilogue, a.bf16_row_kernels)
+         a.bf16_fused_epilogue, a.bf16_row_kernels, a.bf16_rowsk_kernels)

@@ -1,13 +1,15 @@
-"""The bf16 row-streaming conv kernel against the bf16 tile kernel and the fp32 entry on the two layer
-classes it was written for (ResNet56 @224, batch 256: 16 -> 16 @224 and 32 -> 32 @112, 3x3, pad 1):
+"""The bf16 row-streaming conv kernels against the bf16 tile kernel and the fp32 entry on the layer classes
+they were written for (ResNet56 @224, batch 256: 16 -> 16 @224, 32 -> 32 @112 and 64 -> 64 @56, 3x3, pad 1):
 
     python tools/bf16_rows_bench.py [--out profiles/bf16_rows.jsonl --reps 40 --warmup 10 --batch 256 --runs 2]
+    python tools/bf16_rows_bench.py --layers 64@56,64@28,64@14,64@8 --out profiles/bf16_rowsk.jsonl
 
 Three arms, alternated call by call in one process (time_arms of tools/bf16_conv_bench.py), HIP events
 around each whole call (weight quantize + pack launches and the conv, as a model forward issues them):
   fp32   _lib.qconv2d / _lib.qconv2d_fused on fp32 tensors, the autotuned plan
-  tile   _lib.qconv2d_bf16 / _lib.qconv2d_fused_bf16 with the row kernels switched off (conv_bf16x1)
-  rows   the same call with _lib.set_bf16_row_kernels(True) (conv_b16_rows)
+  tile   _lib.qconv2d_bf16 / _lib.qconv2d_fused_bf16 with both row-kernel switches off (conv_bf16x1)
+  rows   the same call with _lib.set_bf16_row_kernels(True) and _lib.set_bf16_rowsk_kernels(True)
+         (conv_b16_rows at C = 16 / 32, conv_b16_rowsk at C = 64)
 Three forms per layer: the plain conv, the conv with a folded eval BatchNorm + ReLU in its store, and the
 same with a residual added before the ReLU.  Every (layer, form) is timed --runs times; one JSON line per
 (layer, form) with each run's median and minimum microseconds per arm, the spread (the largest difference
@@ -30,7 +32,7 @@ from bf16_conv_bench import HBM_BYTES_PER_S, algorithmic_bytes, time_arms  # noq
 from po2_quantization_amd import _lib  # noqa: E402
 from po2_quantization_amd.models.quantized_conv import fold_bn_f32  # noqa: E402
 
-SHAPES = [(16, 224), (32, 112)]  # (C = K, H = W)
+LAYERS = "16@224,32@112"  # C = K @ H = W; --layers 64@56 for stage 3
 FORMS = ["plain", "bn+relu", "bn+add+relu"]
 
 
@@ -42,14 +44,16 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--bits", type=int, default=4)
     ap.add_argument("--runs", type=int, default=2)
+    ap.add_argument("--layers", default=LAYERS, help="comma-separated C@H layers (C = K, H = W)")
     a = ap.parse_args()
+    shapes = [tuple(int(v) for v in item.split("@")) for item in a.layers.split(",")]
     if not torch.cuda.is_available():
         raise SystemExit("bf16_rows_bench: no HIP device (timings are taken on the GPU only)")
     dev = torch.device("cuda:0")
     _lib.benchmark = True  # the fp32 entry autotunes on its first call
     N = a.batch
     lines = []
-    for C, H in SHAPES:
+    for C, H in shapes:
         torch.manual_seed(0)
         x32 = torch.randn(N, C, H, H, device=dev)
         w32 = torch.randn(C, C, 3, 3, device=dev) * 0.1
@@ -63,9 +67,9 @@ def main():
         ps, pb = fold_bn_f32(bn.to(dev).eval())
         r32 = torch.randn(N, C, H, H, device=dev)
         r16 = r32.to(torch.bfloat16)
-        with _lib.bf16_rows(False):
+        with _lib.bf16_rows(False), _lib.bf16_rowsk(False):
             tile_plan = _lib.describe_bf16(N, C, H, H, C, 3, 3, 1, 1, 1, 1, a.bits, "po2")
-        with _lib.bf16_rows(True):
+        with _lib.bf16_rows(True), _lib.bf16_rowsk(True):
             rows_plan = _lib.describe_bf16(N, C, H, H, C, 3, 3, 1, 1, 1, 1, a.bits, "po2")
         for form in FORMS:
             res32, res16 = (r32, r16) if form == "bn+add+relu" else (None, None)
@@ -83,11 +87,11 @@ def main():
                                                post_shift=pb, residual=res16, act="relu")
 
             def tile():
-                with _lib.bf16_rows(False):
+                with _lib.bf16_rows(False), _lib.bf16_rowsk(False):
                     return bf16()
 
             def rows():
-                with _lib.bf16_rows(True):
+                with _lib.bf16_rows(True), _lib.bf16_rowsk(True):
                     return bf16()
 
             arms = {"fp32": fp32, "tile": tile, "rows": rows}
