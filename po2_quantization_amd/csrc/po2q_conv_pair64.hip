@@ -17,7 +17,10 @@
 //     outside the image and columns >= W (conv 2's padding), recomputed rows at a segment's halo;
 //   * A, per step: conv 2's MFMAs from that ring, epilogue 2 and the stores, two groups' values
 //     exchanged by one row_ror:8 DPP move each so a store covers whole 128-byte runs;
-//   * one s_barrier per step, the same count in both roles through the fill and drain steps.
+//   * one s_barrier per step, the same count in both roles through the fill and drain steps;
+//   * PIPE (the default): B issues that vector work in slices between its own MFMAs (mfmas_pipe), so both
+//     waves of a SIMD offer the matrix pipe MFMAs for the whole step; without it (PO2Q_PAIR64_PIPE=0) all
+//     of it comes in front of the MFMAs.  Same values either way.
 // Per accumulator the order is conv_rowsk's (tap row, then k-step, then plane) and the epilogue its
 // expression: the output equals two conv_rowsk launches bit for bit.
 #include <hip/hip_runtime.h>
@@ -54,6 +57,12 @@ constexpr int kP6PackBytes = 3 * kP6KS * 4 * 64 * 16;  // one conv's packed frag
 // byte offset of channel octet oc of padded pixel P (column P - 1) in a plane: 128 bytes per pixel,
 // octets XOR-swizzled by the pixel (conv_rowsk's k_addr<64>)
 __device__ __forceinline__ int p6_addr(int P, int oc) { return P * 128 + ((oc ^ (P & 7)) << 4); }
+
+// f(integral_constant<int, 0>), ..., f(integral_constant<int, N - 1>) in order
+template <class F, int... R>
+__device__ __forceinline__ void p6_unroll(F&& f, std::integer_sequence<int, R...>) {
+    (f(std::integral_constant<int, R>{}), ...);
+}
 }  // namespace
 
 struct Pair64Args {
@@ -69,7 +78,9 @@ struct Pair64Args {
 
 // NG: 16-column groups per row (4, or 3 when W <= 48: a group wholly past W issues no MFMAs);
 // NTS bit 0: non-temporal stores, bit 1: non-temporal x loads.
-template <int NG, int NTS>
+// PIPE: the conv-1 waves issue their vector work (x DMAs, epilogue 1, the split of the next row) in
+// slices between their own MFMAs instead of in front of them; same values, same order per accumulator.
+template <int NG, int NTS, bool PIPE>
 __global__ __launch_bounds__(512, 1) void conv_pair64(const float* __restrict__ x, float* __restrict__ y,
                                                       Pair64Args a) {
     static_assert(NG == 3 || NG == 4, "column groups");
@@ -135,15 +146,17 @@ __global__ __launch_bounds__(512, 1) void conv_pair64(const float* __restrict__ 
         vi[i] = q < a.W ? ((uint32_t)c * (uint32_t)HW + (uint32_t)q) * 4u : 0x7fffffffu;
     }
     const uint32_t raw_lds = (uint32_t)(uintptr_t)raw;
-    auto load_x = [&](int sl, int jn) __attribute__((always_inline)) {
+    auto load_x1 = [&](int sl, int jn, int i) __attribute__((always_inline)) {  // DMA instruction i of a row
         const int h = p0 - 2 + jn;
         const bool hok = jn < nx && h >= 0 && h < a.H;
         const uint32_t roff = (uint32_t)(hok ? h : 0) * (uint32_t)a.W * 4u;
         const uint32_t base = raw_lds + (uint32_t)(sl * kP6Raw) + (uint32_t)(16 * t) * (uint32_t)RPB;
+        rows_dma16<(NTS & 2) != 0>(rs, (hok && vi[i] != 0x7fffffffu) ? vi[i] + roff : 0x7fffffffu, 0u,
+                                   base + (uint32_t)i * 1024u);
+    };
+    auto load_x = [&](int sl, int jn) __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-            rows_dma16<(NTS & 2) != 0>(rs, (hok && vi[i] != 0x7fffffffu) ? vi[i] + roff : 0x7fffffffu, 0u,
-                                       base + (uint32_t)i * 1024u);
+        for (int i = 0; i < 4; ++i) load_x1(sl, jn, i);
     };
     // LDS addresses: one per-lane base VGPR per access pattern, opaque to the compiler, + compile-time
     // offsets that fit the instructions' 16-bit immediates (the regions past 64 KiB otherwise cost an
@@ -151,19 +164,25 @@ __global__ __launch_bounds__(512, 1) void conv_pair64(const float* __restrict__ 
     // ---- B: the exact split of this wave's 16 channels of a raw row: lane = column, octets 2t, 2t + 1
     int xwb[2] = {p6_addr(lane + 1, 2 * t) + kP6PD * kP6Raw, p6_addr(lane + 1, 2 * t + 1) + kP6PD * kP6Raw};
     asm volatile("" : "+v"(xwb[0]), "+v"(xwb[1]));
+    auto split_rd = [&](const unsigned char* rw, int o, uint32_t (&b8)[8]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            b8[e] = *reinterpret_cast<const uint32_t*>(rw + (16 * t + 8 * o + e) * RPB + lane * 4);
+    };
+    auto split_wr = [&](int o, int pb, const uint32_t (&b8)[8]) __attribute__((always_inline)) {
+        uint4 hi, mid, lo;
+        split3(b8, hi, mid, lo);
+        unsigned char* pw = lds + (xwb[o] + pb);
+        *reinterpret_cast<uint4*>(pw) = hi;
+        *reinterpret_cast<uint4*>(pw + PL) = mid;
+        *reinterpret_cast<uint4*>(pw + 2 * PL) = lo;
+    };
     auto split_x = [&](const unsigned char* rw, int pb) __attribute__((always_inline)) {
 #pragma unroll
         for (int o = 0; o < 2; ++o) {
             uint32_t b8[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-                b8[e] = *reinterpret_cast<const uint32_t*>(rw + (16 * t + 8 * o + e) * RPB + lane * 4);
-            uint4 hi, mid, lo;
-            split3(b8, hi, mid, lo);
-            unsigned char* pw = lds + (xwb[o] + pb);
-            *reinterpret_cast<uint4*>(pw) = hi;
-            *reinterpret_cast<uint4*>(pw + PL) = mid;
-            *reinterpret_cast<uint4*>(pw + 2 * PL) = lo;
+            split_rd(rw, o, b8);
+            split_wr(o, pb, b8);
         }
     };
 
@@ -224,6 +243,41 @@ __global__ __launch_bounds__(512, 1) void conv_pair64(const float* __restrict__ 
         }
     };
 
+    // The same MFMAs (conv 1, transposed) with the step's vector slices between them: pre(st) runs in
+    // front of stage st's fragment reads (the DMA issues: their lgkmcnt(0) then finds no read in flight
+    // but the ones the stage's MFMAs wait for anyway), hook(3 st + rr) after the NG MFMAs of tap row rr.
+    // One scheduling region per tap row keeps the emitted order.
+    auto mfmas_pipe = [&](auto S_, int pb, auto&& pre, auto&& hook) __attribute__((always_inline)) {
+        constexpr int S = decltype(S_)::value;
+        constexpr int SL[3] = {(S + 1) % 3, S, (S + 2) % 3};
+        bf16x8 af[2][NG];
+        auto ldf = [&](bf16x8 (&f)[NG], int st) __attribute__((always_inline)) {
+#pragma unroll
+            for (int grp = 0; grp < NG; ++grp)
+                f[grp] = __builtin_bit_cast(
+                    bf16x8, *reinterpret_cast<const uint4*>(lds + (foff[st / 3] + (pb + (st % 3) * PL + grp * (16 * 128)))));
+        };
+        ldf(af[0], 0);
+        auto stage = [&](auto ST_) __attribute__((always_inline)) {
+            constexpr int st = decltype(ST_)::value;
+            constexpr int ks = st / 3;
+            pre(ST_);
+            if constexpr (st + 1 < 3 * KS) ldf(af[(st + 1) & 1], st + 1);
+            __builtin_amdgcn_sched_barrier(0);
+            auto row = [&](auto RR_) __attribute__((always_inline)) {
+                constexpr int rr = decltype(RR_)::value;
+#pragma unroll
+                for (int grp = 0; grp < NG; ++grp)
+                    acc[SL[rr]][grp] =
+                        __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[rr][ks], af[st & 1][grp], acc[SL[rr]][grp], 0, 0, 0);
+                hook(std::integral_constant<int, 3 * st + rr>{});
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            p6_unroll(row, std::make_integer_sequence<int, 3>{});
+        };
+        p6_unroll(stage, std::make_integer_sequence<int, 3 * KS>{});
+    };
+
     // B: conv 1's completed accumulator slot, held until the next step's epilogue 1
     floatx4 pend[NG];
 #pragma unroll
@@ -239,37 +293,65 @@ __global__ __launch_bounds__(512, 1) void conv_pair64(const float* __restrict__ 
         constexpr int B2 = S6 & 1;        // x plane set of row j, raw slot of rows j and j + 2
         // everyone's reads of the sets written below have retired; row j's planes are published
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        load_x(B2, j + 2);
-        {
-            const int i1 = j - 3;
-            const int r1 = p0 - 1 + i1;
-            const bool irow = i1 >= 0 && i1 < n1 && r1 >= 0 && r1 < a.H;
-            const int p = lane & 15;
-            unsigned char* yw = lds + (ywb + (1 - B2) * SET);
+        const int i1 = j - 3;
+        const int r1 = p0 - 1 + i1;
+        const bool irow = i1 >= 0 && i1 < n1 && r1 >= 0 && r1 < a.H;
+        unsigned char* yw = lds + (ywb + (1 - B2) * SET);
+        auto epi1 = [&](int grp) __attribute__((always_inline)) {
+            const int q = 16 * grp + (lane & 15);  // lane: pixel q, channels 16t + 4g .. + 3
+            const bool okq = irow && q < a.W;
+            uint32_t b4[4];
 #pragma unroll
-            for (int grp = 0; grp < NG; ++grp) {
-                const int q = 16 * grp + p;  // lane: pixel q, channels 16t + 4g .. + 3
-                const bool okq = irow && q < a.W;
-                uint32_t b4[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float v = pend[grp][e] * scale + bk[e];
-                    b4[e] = okq ? __float_as_uint(v) : 0u;  // conv 2's zero padding
-                }
-                uint2 h2, m2, l2;
-                split4p(b4, h2, m2, l2);
-                unsigned char* yg = yw + grp * (16 * 128);
-                *reinterpret_cast<uint2*>(yg) = h2;
-                *reinterpret_cast<uint2*>(yg + PL) = m2;
-                *reinterpret_cast<uint2*>(yg + 2 * PL) = l2;
+            for (int e = 0; e < 4; ++e) {
+                const float v = pend[grp][e] * scale + bk[e];
+                b4[e] = okq ? __float_as_uint(v) : 0u;  // conv 2's zero padding
             }
-        }
-        rows_wait<4>();  // this wave's DMAs of row j + 1 have landed (row j + 2's may fly)
-        split_x(raw + (1 - B2) * kP6Raw, (1 - B2) * SET);
-        {
-            // x rows outside the image / segment are zeros: their MFMAs would add exact zeros
-            const int h = p0 - 2 + j;
-            if (j < nx && h >= 0 && h < a.H) mfmas(std::integral_constant<int, S>{}, std::true_type{}, B2 * SET);
+            uint2 h2, m2, l2;
+            split4p(b4, h2, m2, l2);
+            unsigned char* yg = yw + grp * (16 * 128);
+            *reinterpret_cast<uint2*>(yg) = h2;
+            *reinterpret_cast<uint2*>(yg + PL) = m2;
+            *reinterpret_cast<uint2*>(yg + 2 * PL) = l2;
+        };
+        // x rows outside the image / segment are zeros: their MFMAs would add exact zeros
+        const int hx = p0 - 2 + j;
+        const bool xrow = j < nx && hx >= 0 && hx < a.H;
+        if constexpr (!PIPE) {
+            load_x(B2, j + 2);
+#pragma unroll
+            for (int grp = 0; grp < NG; ++grp) epi1(grp);
+            rows_wait<4>();  // this wave's DMAs of row j + 1 have landed (row j + 2's may fly)
+            split_x(raw + (1 - B2) * kP6Raw, (1 - B2) * SET);
+            if (xrow) mfmas(std::integral_constant<int, S>{}, std::true_type{}, B2 * SET);
+        } else {
+            // the same work as slices: DMA i in front of stage i; epilogue-1 tile v after MFMA slot 2 v + 1;
+            // then (all four DMAs issued) the counted wait and the raw reads of octet 0, its split two slots
+            // later, and the same for octet 1.  Nothing here touches what this step's MFMAs (either role's)
+            // read: the ring slot and the plane set written are the ones read in the NEXT step.
+            uint32_t b8[8];
+            const unsigned char* rw = raw + (1 - B2) * kP6Raw;
+            auto pre = [&](auto ST_) __attribute__((always_inline)) {
+                constexpr int st = decltype(ST_)::value;
+                if constexpr (st < 4) load_x1(B2, j + 2, st);
+            };
+            auto hook = [&](auto K_) __attribute__((always_inline)) {
+                constexpr int K = decltype(K_)::value;
+                if constexpr (K % 2 == 1 && K / 2 < NG) epi1(K / 2);
+                if constexpr (K == 10) {
+                    rows_wait<4>();  // this wave's DMAs of row j + 1 have landed (row j + 2's may fly)
+                    split_rd(rw, 0, b8);
+                }
+                if constexpr (K == 12) split_wr(0, (1 - B2) * SET, b8);
+                if constexpr (K == 13) split_rd(rw, 1, b8);
+                if constexpr (K == 15) split_wr(1, (1 - B2) * SET, b8);
+            };
+            static_assert(2 * (NG - 1) + 1 < 10, "epilogue-1 tiles come before the split");
+            if (xrow) {
+                mfmas_pipe(std::integral_constant<int, S>{}, B2 * SET, pre, hook);
+            } else {  // no MFMAs to hide under: the slices in the same order
+                p6_unroll(pre, std::make_integer_sequence<int, 4>{});
+                p6_unroll(hook, std::make_integer_sequence<int, 16>{});
+            }
         }
 #pragma unroll
         for (int grp = 0; grp < NG; ++grp) {
@@ -399,13 +481,18 @@ hipError_t pair64_launch(const float* x, float* y, int64_t N, int64_t H, int64_t
     // PO2Q_PAIR64_NTS=3: non-temporal (A/B knob)
     int nts = 0;
     if (const char* e = getenv("PO2Q_PAIR64_NTS")) nts = atoi(e) == 0 ? 0 : 3;
+    // PO2Q_PAIR64_PIPE=0: the conv-1 waves' vector work in front of their MFMAs (the earlier schedule;
+    // A/B knob and the in-build bitwise reference); on by default
+    bool pipe = true;
+    if (const char* e = getenv("PO2Q_PAIR64_PIPE")) pipe = e[0] != '0';
     const dim3 grid((unsigned)blocks), block(512);
-#define PO2Q_P6(g, t)                                                                            \
-    if ((W <= 48 ? 3 : 4) == g && nts == t) {                                                    \
-        hipLaunchKernelGGL((conv_pair64<g, t>), grid, block, (size_t)kP6Lds, s, x, y, a);        \
+#define PO2Q_P6(g, t, p)                                                                         \
+    if ((W <= 48 ? 3 : 4) == g && nts == t && pipe == p) {                                       \
+        hipLaunchKernelGGL((conv_pair64<g, t, p>), grid, block, (size_t)kP6Lds, s, x, y, a);     \
         return hipGetLastError();                                                                \
     }
-    PO2Q_P6(4, 3) PO2Q_P6(3, 3) PO2Q_P6(4, 0) PO2Q_P6(3, 0)
+    PO2Q_P6(4, 0, true) PO2Q_P6(3, 0, true) PO2Q_P6(4, 3, true) PO2Q_P6(3, 3, true)
+    PO2Q_P6(4, 0, false) PO2Q_P6(3, 0, false) PO2Q_P6(4, 3, false) PO2Q_P6(3, 3, false)
 #undef PO2Q_P6
     return hipErrorInvalidValue;
 }

@@ -22,6 +22,9 @@
 //     waves issue their MFMAs, then their vector work, at the same time.
 // At W = 112 strip 3's second group (columns 112-127) is image padding: its MFMAs run on zeros and its
 // stores are dropped, so every SIMD carries the same 2 groups of both convs.
+// PIPE (the default without a residual; PO2Q_PAIR_W32_PIPE=0 turns it off): B splits x one row ahead into
+// a second plane set of its strip and issues epilogue 1 and that split in slices between the MFMAs of
+// the row split a step earlier, so both waves of a SIMD offer the matrix pipe MFMAs for the whole step.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -80,12 +83,18 @@ struct PairWArgs {
 // PD: x ring slots (2 or 3); NTS bit 0: non-temporal stores, bit 1: non-temporal x loads.
 // E: 0 = plain chain (y = scale * acc), 1 = general epilogues, 2 = the BasicBlock form (ReLU after both
 // BNs, the conv scale and bias folded into the BN affine at staging).
+// PIPE: the conv-1 waves split x one row ahead into a double-buffered slab (a second plane set per strip)
+// and issue epilogue 1 and that split in slices between the MFMAs of the row split a step earlier; same
+// values, same order per accumulator.  Not with RES (the residual slots leave no room for the second
+// plane sets: that form keeps the schedule below).
 // DBG (diagnostic builds only, -DPO2Q_PAIRW_DIAG, PO2Q_PAIR_W32_DBG; timing only, outputs are wrong):
 // bit 1 no MFMAs, 2 no x DMAs, 4 no stores, 8 no epilogue / split vector work, 16 no per-step barrier.
-template <int PD, int NTS, bool RES, int E, int DBG = 0>
+template <int PD, int NTS, bool RES, int E, bool PIPE, int DBG = 0>
 __global__ __launch_bounds__(512, 1) void conv_pairw(const float* __restrict__ x, float* __restrict__ y,
                                                      PairWArgs a) {
     static_assert(PD >= 2 && PD <= 5, "raw ring slots");
+    static_assert(!PIPE || (PD == 2 && !RES && DBG == 0), "the pipelined schedule: 2 raw slots, no residual");
+    constexpr int NSET = PIPE ? 2 : 1;  // x plane sets per strip
     constexpr int CC = kPWC, SW = kPWSW, WC = SW + 2, PL = kPWPL, YPL = kPWYPL, RPB = kPWRPB;
     constexpr int NG = SW / 16, NT = CC / 16, KS = 3, NF = 3 * KS * NT;
     constexpr int yslot = 3 * YPL;
@@ -96,8 +105,8 @@ __global__ __launch_bounds__(512, 1) void conv_pairw(const float* __restrict__ x
     const int sw = wave & (kPWWaves - 1);  // strip
     unsigned char* raw = lds;                                             // PD x [32][128] fp32
     unsigned char* yr = raw + PD * kPWRaw;                                // 2 x 3 planes (intermediate)
-    unsigned char* slab = yr + 2 * yslot + sw * (3 * PL);                 // B: this strip's x planes
-    unsigned char* resr = yr + 2 * yslot + kPWWaves * 3 * PL + sw * (PD * kPWRes);  // A: residual slots
+    unsigned char* slab = yr + 2 * yslot + sw * (NSET * 3 * PL);          // B: this strip's x planes
+    unsigned char* resr = yr + 2 * yslot + kPWWaves * NSET * 3 * PL + sw * (PD * kPWRes);  // A: residual slots
 
     int blk = blockIdx.x;
     if (a.remap) blk = (blk & 7) * (int)(gridDim.x >> 3) + (blk >> 3);
@@ -183,7 +192,8 @@ __global__ __launch_bounds__(512, 1) void conv_pairw(const float* __restrict__ x
     constexpr int ST = 2 * NT;  // A's stores per step (whole-line pairs; dropped ones out of range)
     // counted waits at the top of a step: B waits for its DMAs of x row j (issued PD - 1 steps
     // earlier; its later DMAs may fly), A (RES) for its residual DMAs of the row it stores at step j
-    constexpr int VMW_B = 4 * (PD - 2);
+    // (PIPE: row j + 1, issued in step j - 1 and the last issued: nothing may fly)
+    constexpr int VMW_B = PIPE ? 0 : 4 * (PD - 2);
     constexpr int VMW_A = ST + (PD - 2) * (4 + ST);
 
     float scale = 1.0f;  // this wave's conv: scale1 (B) or scale2 (A)
@@ -253,6 +263,140 @@ __global__ __launch_bounds__(512, 1) void conv_pairw(const float* __restrict__ x
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) pend[grp][nt] = floatx4{0.f, 0.f, 0.f, 0.f};
 
+    // ---- the slices of B's vector work.  Epilogue 1 of tile (grp, nt): affine / activation, zeros outside
+    // the image (conv 2's padding), exact split
+    auto epi1 = [&](unsigned char* yw, bool irow, int grp, int nt) __attribute__((always_inline)) {
+        const int p = lane & 15, g = lane >> 4;
+        const int q = q0 + 16 * grp + p;  // lane: pixel q, channels 16 nt + 4 g .. + 3
+        const bool okq = irow && q < a.W;
+        uint32_t b4[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float t;
+            if constexpr (E == 0) {
+                t = pend[grp][nt][e] * scale + 0.0f;
+            } else if constexpr (E == 2) {
+                const int c = nt * 4 + e;
+                t = pend[grp][nt][e] * es[c] + eb[c];  // folded affine, then ReLU
+                t = t < 0.0f ? 0.0f : t;
+            } else {
+                const int c = nt * 4 + e;
+                t = epi_act((pend[grp][nt][e] * scale + bk[c]) * es[c] + eb[c], a.act1);
+            }
+            b4[e] = okq ? __float_as_uint(t) : 0u;
+        }
+        uint2 h2, m2, l2;
+        split4p<false>(b4, h2, m2, l2);
+        const int wo = pw_oct(q + 1, (4 * nt + g) >> 1) + 8 * (g & 1);
+        *reinterpret_cast<uint2*>(yw + wo) = h2;
+        *reinterpret_cast<uint2*>(yw + YPL + wo) = m2;
+        *reinterpret_cast<uint2*>(yw + 2 * YPL + wo) = l2;
+    };
+    // the raw reads of a row (both columns of the lane's pair per channel, the halo value), the exact
+    // split of column half h into plane set sp, the halo column's split
+    auto raw_rd = [&](const unsigned char* rw, uint32_t (&bx)[2][8], uint32_t& hx) __attribute__((always_inline)) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const uint2 v2 = *reinterpret_cast<const uint2*>(rw + rdx0 + e * RPB);
+            bx[0][e] = v2.x;
+            bx[1][e] = v2.y;
+        }
+        hx = *reinterpret_cast<const uint32_t*>(rw + rdx_h);
+    };
+    auto split_half = [&](unsigned char* sp, int h, const uint32_t (&bx)[2][8]) __attribute__((always_inline)) {
+        const int wa = h ? wa1 : wa0;
+        uint4 hi, mid, lo;
+        split3<false>(bx[h], hi, mid, lo);
+        *reinterpret_cast<uint4*>(sp + wa) = hi;
+        *reinterpret_cast<uint4*>(sp + PL + wa) = mid;
+        *reinterpret_cast<uint4*>(sp + 2 * PL + wa) = lo;
+    };
+    auto split_halo = [&](unsigned char* sp, uint32_t hx) __attribute__((always_inline)) {
+        uint16_t h16, m16, l16;
+        split1(h_ok ? hx : 0u, h16, m16, l16);
+        *reinterpret_cast<uint16_t*>(sp + wa_h) = h16;
+        *reinterpret_cast<uint16_t*>(sp + PL + wa_h) = m16;
+        *reinterpret_cast<uint16_t*>(sp + 2 * PL + wa_h) = l16;
+    };
+
+    // conv 1's 108 MFMAs as mfmas() issues them, in 18 units of 6 (one fragment each), hook(u) after unit
+    // u's MFMAs and in front of its fragment's refill; one scheduling region per unit keeps the order
+    auto mfmas_pipe = [&](auto S_, const unsigned char* pb, auto&& hook) __attribute__((always_inline)) {
+        constexpr int SR = decltype(S_)::value;
+        constexpr int SL[3] = {(SR + 1) % 3, SR, (SR + 2) % 3};
+        bf16x8 af[3][NG];
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+            for (int grp = 0; grp < NG; ++grp)
+                af[pl][grp] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(pb + pl * PL + foff[grp][0]));
+        auto unit = [&](auto U_) __attribute__((always_inline)) {
+            constexpr int u = decltype(U_)::value;
+            constexpr int ks = u / (3 * NG), pl = (u / NG) % 3, grp = u % NG;
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int m = 0; m < 6; ++m) {  // (r3, nt): tap row 2 first
+                const int r3 = m / NT, nt = m % NT;
+                const int rr = 2 - r3;
+                const bf16x8 b = bw[(rr * KS + ks) * NT + nt];
+                const floatx4 c = (rr == 0 && ks == 0 && pl == 0) ? floatx4{0.f, 0.f, 0.f, 0.f} : acc[SL[rr]][grp][nt];
+                acc[SL[rr]][grp][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, af[pl][grp], c, 0, 0, 0);
+            }
+            hook(U_);
+            if constexpr (ks + 1 < KS)
+                af[pl][grp] = __builtin_bit_cast(
+                    bf16x8, *reinterpret_cast<const uint4*>(pb + pl * PL + foff[grp][ks + 1 < KS ? ks + 1 : 0]));
+        };
+        pw_unroll(unit, std::make_integer_sequence<int, 3 * KS * NG>{});
+        __builtin_amdgcn_sched_barrier(0);
+    };
+
+    // ---- B, pipelined, step j: the x DMAs of row j + 2 into the raw slot of row j (split in step j - 1),
+    // then between the MFMAs of row j (plane set j & 1): epilogue 1 of intermediate row j - 3 (pend) into
+    // ring slot YW, the raw reads of row j + 1 and its split into plane set (j + 1) & 1 (the raw values die
+    // within four units: the general form has no registers to hold them longer).  Nothing a slice writes
+    // is read by anyone in this step.
+    auto stepBP = [&](auto S_, int j) __attribute__((always_inline)) {
+        constexpr int S6 = decltype(S_)::value;
+        constexpr int S = S6 % 3;
+        constexpr int D = (S + 2) % 3;          // the accumulator slot that completes
+        constexpr int YW = (S6 + 1) & 1;        // ring slot written: intermediate row j - 3
+        constexpr int P = S6 & 1;               // j & 1: plane set of row j, raw slot of rows j and j + 2
+        rows_wait<VMW_B>();  // this wave's part of x row j + 1 has landed
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // + everyone's reads of the slot refilled
+        load_x(P, j + 2);
+        const int i1 = j - 3;
+        const int r1 = p0 - 1 + i1;
+        const bool irow = i1 >= 0 && i1 < n1 && r1 >= 0 && r1 < a.H;
+        unsigned char* yw = yr + YW * yslot;
+        const unsigned char* rw = raw + (1 - P) * kPWRaw;
+        unsigned char* sp = slab + (1 - P) * (3 * PL);
+        uint32_t bx[2][8], hx;
+        auto hook = [&](auto U_) __attribute__((always_inline)) {
+            constexpr int u = decltype(U_)::value;
+            if constexpr (u == 0) epi1(yw, irow, 0, 0);
+            if constexpr (u == 1) raw_rd(rw, bx, hx);
+            if constexpr (u == 3) split_half(sp, 0, bx);
+            if constexpr (u == 4) split_half(sp, 1, bx);
+            if constexpr (u == 5) split_halo(sp, hx);
+            if constexpr (u == 7) epi1(yw, irow, 0, 1);
+            if constexpr (u == 9) epi1(yw, irow, 1, 0);
+            if constexpr (u == 11) epi1(yw, irow, 1, 1);
+        };
+        static_assert(NG == 2 && NT == 2, "the slice table");
+        const int h = p0 - 2 + j;
+        if (j < nx && h >= 0 && h < a.H) {
+            mfmas_pipe(std::integral_constant<int, S>{}, slab + P * (3 * PL), hook);
+        } else {  // a skipped row: the slices in the same order
+            pw_unroll(hook, std::make_integer_sequence<int, 12>{});
+            zero_slot(std::integral_constant<int, S>{});
+        }
+#pragma unroll
+        for (int grp = 0; grp < NG; ++grp)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) pend[grp][nt] = acc[D][grp][nt];
+    };
+
     // ---- B, step j: epilogue 1 of intermediate row j - 3 (pend, completed at step j - 1) into ring slot
     // YW, the exact split of x row j, conv 1 on it (intermediate row j - 2 completes into pend)
     auto stepB = [&](auto S_, int j) __attribute__((always_inline)) {
@@ -287,68 +431,21 @@ __global__ __launch_bounds__(512, 1) void conv_pairw(const float* __restrict__ x
             load_x((6 % PD == 0) ? (S6 + PD - 1) % PD : (j - 1 + PD) % PD, j - 1 + PD);
         }
         uint32_t bx[2][8], hx;
-        {
-            const unsigned char* rw = raw + RS * kPWRaw;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const uint2 v2 = *reinterpret_cast<const uint2*>(rw + rdx0 + e * RPB);
-                bx[0][e] = v2.x;
-                bx[1][e] = v2.y;
-            }
-            hx = *reinterpret_cast<const uint32_t*>(rw + rdx_h);
-        }
+        raw_rd(raw + RS * kPWRaw, bx, hx);
         if constexpr ((DBG & 8) == 0) {  // epilogue 1: affine / activation, zeros outside the image (conv 2's padding), exact split
             const int i1 = j - 3;
             const int r1 = p0 - 1 + i1;
             const bool irow = i1 >= 0 && i1 < n1 && r1 >= 0 && r1 < a.H;
-            const int p = lane & 15, g = lane >> 4;
             unsigned char* yw = yr + YW * yslot;
 #pragma unroll
-            for (int grp = 0; grp < NG; ++grp) {
-                const int q = q0 + 16 * grp + p;  // lane: pixel q, channels 16 nt + 4 g .. + 3
-                const bool okq = irow && q < a.W;
+            for (int grp = 0; grp < NG; ++grp)
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    uint32_t b4[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float t;
-                        if constexpr (E == 0) {
-                            t = pend[grp][nt][e] * scale + 0.0f;
-                        } else if constexpr (E == 2) {
-                            const int c = nt * 4 + e;
-                            t = pend[grp][nt][e] * es[c] + eb[c];  // folded affine, then ReLU
-                            t = t < 0.0f ? 0.0f : t;
-                        } else {
-                            const int c = nt * 4 + e;
-                            t = epi_act((pend[grp][nt][e] * scale + bk[c]) * es[c] + eb[c], a.act1);
-                        }
-                        b4[e] = okq ? __float_as_uint(t) : 0u;
-                    }
-                    uint2 h2, m2, l2;
-                    split4p<false>(b4, h2, m2, l2);
-                    const int wo = pw_oct(q + 1, (4 * nt + g) >> 1) + 8 * (g & 1);
-                    *reinterpret_cast<uint2*>(yw + wo) = h2;
-                    *reinterpret_cast<uint2*>(yw + YPL + wo) = m2;
-                    *reinterpret_cast<uint2*>(yw + 2 * YPL + wo) = l2;
-                }
-            }
+                for (int nt = 0; nt < NT; ++nt) epi1(yw, irow, grp, nt);
         }
         if constexpr ((DBG & 8) == 0) {  // the exact split of x row j into the strip's planes
-            uint4 hi, mid, lo;
-            split3<false>(bx[0], hi, mid, lo);
-            *reinterpret_cast<uint4*>(slab + wa0) = hi;
-            *reinterpret_cast<uint4*>(slab + PL + wa0) = mid;
-            *reinterpret_cast<uint4*>(slab + 2 * PL + wa0) = lo;
-            split3<false>(bx[1], hi, mid, lo);
-            *reinterpret_cast<uint4*>(slab + wa1) = hi;
-            *reinterpret_cast<uint4*>(slab + PL + wa1) = mid;
-            *reinterpret_cast<uint4*>(slab + 2 * PL + wa1) = lo;
-            uint16_t h16, m16, l16;
-            split1(h_ok ? hx : 0u, h16, m16, l16);
-            *reinterpret_cast<uint16_t*>(slab + wa_h) = h16;
-            *reinterpret_cast<uint16_t*>(slab + PL + wa_h) = m16;
-            *reinterpret_cast<uint16_t*>(slab + 2 * PL + wa_h) = l16;
+            split_half(slab, 0, bx);
+            split_half(slab, 1, bx);
+            split_halo(slab, hx);
         }
         if constexpr ((DBG & 1) == 0) {
             // x rows outside the image (the fill steps' padding rows, past the segment) are zeros: their
@@ -447,7 +544,7 @@ __global__ __launch_bounds__(512, 1) void conv_pairw(const float* __restrict__ x
     // ST dropped stores (A's steady-state count)
     if (!roleA) {
 #pragma unroll
-        for (int r = 0; r < PD - 1; ++r) load_x(r, r);
+        for (int r = 0; r < (PIPE ? 2 : PD - 1); ++r) load_x(r, r);  // PIPE: rows 0 and 1 in flight
     } else if constexpr (RES) {
         const floatx4 z = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -517,6 +614,16 @@ __global__ __launch_bounds__(512, 1) void conv_pairw(const float* __restrict__ x
         for (int e = tid; e < (2 * yslot) / 16; e += blockDim.x)
             reinterpret_cast<uint4*>(yr)[e] = make_uint4(0u, 0u, 0u, 0u);
         // step 0's barrier publishes the zeros
+        if constexpr (PIPE) {
+            // row 0 landed for every wave (the vmcnt(0) and the barrier above): split it into plane set 0
+            if (!roleA) {
+                uint32_t bx[2][8], hx;
+                raw_rd(raw, bx, hx);
+                split_half(slab, 0, bx);
+                split_half(slab, 1, bx);
+                split_halo(slab, hx);
+            }
+        }
     }
     (void)fin;
     if constexpr ((DBG & 64) != 0) return;  // probe: launch + weight staging only
@@ -532,13 +639,16 @@ __global__ __launch_bounds__(512, 1) void conv_pairw(const float* __restrict__ x
         }
     } else {
         for (int j = 0; j < nsteps; j += 6) {
-            stepB(std::integral_constant<int, 0>{}, j);
-            stepB(std::integral_constant<int, 1>{}, j + 1);
-            stepB(std::integral_constant<int, 2>{}, j + 2);
+            auto step = [&](auto S_, int jj) __attribute__((always_inline)) {
+                if constexpr (PIPE) stepBP(S_, jj); else stepB(S_, jj);
+            };
+            step(std::integral_constant<int, 0>{}, j);
+            step(std::integral_constant<int, 1>{}, j + 1);
+            step(std::integral_constant<int, 2>{}, j + 2);
             if (j + 3 >= nsteps) break;
-            stepB(std::integral_constant<int, 3>{}, j + 3);
-            stepB(std::integral_constant<int, 4>{}, j + 4);
-            stepB(std::integral_constant<int, 5>{}, j + 5);
+            step(std::integral_constant<int, 3>{}, j + 3);
+            step(std::integral_constant<int, 4>{}, j + 4);
+            step(std::integral_constant<int, 5>{}, j + 5);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // trailing DMAs / stores land before the wave ends
@@ -546,13 +656,14 @@ __global__ __launch_bounds__(512, 1) void conv_pairw(const float* __restrict__ x
 
 namespace {
 
-size_t pairw_lds(int pd, bool res) {
-    return (size_t)pd * kPWRaw + 2 * 3 * (size_t)kPWYPL + (size_t)kPWWaves * 3 * kPWPL +
+size_t pairw_lds(int pd, bool res, bool pipe) {
+    return (size_t)pd * kPWRaw + 2 * 3 * (size_t)kPWYPL + (size_t)kPWWaves * (pipe ? 2 : 1) * 3 * kPWPL +
            (res ? (size_t)kPWWaves * pd * kPWRes : 0);
 }
 
 template <int PD, int NTS>
-hipError_t launch_pairw_t(int blocks, size_t lds, const PairWArgs& a, const float* x, float* y, bool res, hipStream_t s) {
+hipError_t launch_pairw_t(int blocks, size_t lds, const PairWArgs& a, const float* x, float* y, bool res, bool pipe,
+                          hipStream_t s) {
     const bool plain = !res && !a.b1 && !a.b2 && !a.ps1 && !a.pb1 && !a.ps2 && !a.pb2 && a.act1 == 0 && a.act2 == 0;
     const dim3 grid((unsigned)blocks), block(64 * 2 * kPWWaves);
 #ifdef PO2Q_PAIRW_DIAG
@@ -560,7 +671,7 @@ hipError_t launch_pairw_t(int blocks, size_t lds, const PairWArgs& a, const floa
         const int dbg = atoi(dv);
 #define PO2Q_PWD(v) \
         if (dbg == v && plain && NTS == 3) { \
-            hipLaunchKernelGGL((conv_pairw<PD, NTS, false, 0, v>), grid, block, lds, s, x, y, a); \
+            hipLaunchKernelGGL((conv_pairw<PD, NTS, false, 0, false, v>), grid, block, lds, s, x, y, a); \
             return hipGetLastError(); \
         }
         PO2Q_PWD(9) PO2Q_PWD(11) PO2Q_PWD(13) PO2Q_PWD(15) PO2Q_PWD(25) PO2Q_PWD(29) PO2Q_PWD(27)
@@ -568,17 +679,19 @@ hipError_t launch_pairw_t(int blocks, size_t lds, const PairWArgs& a, const floa
 #undef PO2Q_PWD
     }
 #endif
-    if (plain) {
-        hipLaunchKernelGGL((conv_pairw<PD, NTS, false, 0>), grid, block, lds, s, x, y, a);
-        return hipGetLastError();
-    }
-    if constexpr (PD == 2) {  // the residual slots leave room for 2 x slots only
-        if (res && a.act1 == 1 && a.act2 == 1)  // the BasicBlock form (resnet.py:55-71): ReLU / ReLU
-            hipLaunchKernelGGL((conv_pairw<PD, NTS, true, 2>), grid, block, lds, s, x, y, a);
+    if constexpr (PD == 2) {  // the residual slots and the second plane sets leave room for 2 x slots only
+        if (plain && pipe)
+            hipLaunchKernelGGL((conv_pairw<PD, NTS, false, 0, true>), grid, block, lds, s, x, y, a);
+        else if (plain)
+            hipLaunchKernelGGL((conv_pairw<PD, NTS, false, 0, false>), grid, block, lds, s, x, y, a);
+        else if (res && a.act1 == 1 && a.act2 == 1)  // the BasicBlock form (resnet.py:55-71): ReLU / ReLU
+            hipLaunchKernelGGL((conv_pairw<PD, NTS, true, 2, false>), grid, block, lds, s, x, y, a);
         else if (res)
-            hipLaunchKernelGGL((conv_pairw<PD, NTS, true, 1>), grid, block, lds, s, x, y, a);
+            hipLaunchKernelGGL((conv_pairw<PD, NTS, true, 1, false>), grid, block, lds, s, x, y, a);
+        else if (pipe)
+            hipLaunchKernelGGL((conv_pairw<PD, NTS, false, 1, true>), grid, block, lds, s, x, y, a);
         else
-            hipLaunchKernelGGL((conv_pairw<PD, NTS, false, 1>), grid, block, lds, s, x, y, a);
+            hipLaunchKernelGGL((conv_pairw<PD, NTS, false, 1, false>), grid, block, lds, s, x, y, a);
         return hipGetLastError();
     }
     return hipErrorInvalidValue;
@@ -611,7 +724,14 @@ hipError_t pairw_launch(const float* x, const float* w1, const float* w2, float*
     // after its row's DMA, which temporal loads leave in L2 (conv_pair's variant 21 at C = 16)
     int nts = res ? 1 : 3;
     if (const char* e = getenv("PO2Q_PAIR_W32_NTS")) nts = atoi(e) == 1 ? 1 : 3;
-    const size_t lds = pairw_lds(pd, res);
+    // PO2Q_PAIR_W32_PIPE=0: the conv-1 waves' vector work in front of their MFMAs, one plane set per strip
+    // (the earlier schedule: A/B knob, the in-build bitwise reference, and the residual forms' schedule)
+    bool pipe = !res;
+    if (const char* e = getenv("PO2Q_PAIR_W32_PIPE")) pipe = pipe && e[0] != '0';
+#ifdef PO2Q_PAIRW_DIAG
+    if (getenv("PO2Q_PAIR_W32_DBG")) pipe = false;  // the ablation switches sit in the earlier schedule
+#endif
+    const size_t lds = pairw_lds(pd, res, pipe);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     int nseg = std::max<int64_t>(1, (256 + N - 1) / N);
     nseg = std::min<int>(nseg, std::max<int>(1, (int)H / 8));
@@ -633,7 +753,7 @@ hipError_t pairw_launch(const float* x, const float* w1, const float* w2, float*
     a.ps2 = post_scale2; a.pb2 = post_shift2; a.act2 = act2;
     a.res = residual;
 #define PO2Q_PW(d, t) \
-    if (pd == d && nts == t) return launch_pairw_t<d, t>(blocks, lds, a, x, y, res, s);
+    if (pd == d && nts == t) return launch_pairw_t<d, t>(blocks, lds, a, x, y, res, pipe, s);
     PO2Q_PW(2, 3)
 #ifndef PO2Q_PAIRW_ISA
     PO2Q_PW(2, 1)
