@@ -314,6 +314,42 @@ int po2q_bf16_set_rowsk_kernels(int on);
 int po2q_bf16_rowsk_kernels(void);
 
 /*
+ * Both convs of a BasicBlock with an identity shortcut in one launch (conv_b16_pair, "kind=bf16_pair C=..
+ * RB=.. bands=.. groups=.. GW=.. lds=.. blocks=.."): x -> conv 1 -> epilogue 1 -> conv 2 -> epilogue 2
+ * (+ x) -> y, the intermediate kept on chip.  x and y are bf16 bit patterns, contiguous NCHW [N, C, H, W];
+ * w1 and w2 are [C, C, 3, 3]; both convs are 3x3, stride 1, pad 1, dilation 1, groups 1 and share
+ * (bits, fsr, mode).  Modes none / po2 / po2+; the lin modes are PO2Q_ERR_UNSUPPORTED.
+ * Arithmetic (the contract):
+ *   mid = bf16_rne(act1((acc1 + float(bias1[k])) * post_scale1[k] + post_shift1[k]))
+ *   y   = bf16_rne(act2((acc2 + float(bias2[k])) * post_scale2[k] + post_shift2[k] + float(x[n, k, p, q])))
+ * (the last term only when add_x != 0) with acc1 the fp32 accumulation of the exact products x * Q(w1) and
+ * acc2 that of mid * Q(w2), one v_mfma_f32_16x16x32_bf16 per k-step, Q(w) from the quantize body of
+ * po2q_qconv2d_bf16.  That is two po2q_qconv2d_fused_bf16 calls with residual = x (step order per value:
+ * bias, affine, residual, activation, one rounding) up to the accumulation order.  Conv 2 pads with zeros: a
+ * mid row or column outside the image is zero, never act1(post_shift1); padded taps multiply zeros.
+ * Any pointer except x, w1, w2, y and workspace may be NULL (NULL scale = 1, NULL shift = 0, NULL bias = 0).
+ * y must not alias x.  act1 / act2: enum po2q_act.
+ * Eligible shapes: C in {16, 32}, W even, W <= 256 at C = 16 and W <= 128 at C = 32; anything else is
+ * PO2Q_ERR_UNSUPPORTED and po2q_qconv2d_pair_bf16_supported returns 0 (1 otherwise).  _supported states
+ * eligibility only; it is no speed advisory.  No switch of the bf16 entries is read or written.
+ * The workspace (po2q_qconv2d_pair_bf16_workspace_bytes; 0 with the error set for rejected arguments) holds
+ * both weight packs and their max|w| partials.  Launches: one max|w| launch for both weights (quantized
+ * modes), one quantize + pack launch for both, the pair.  Every error returns before any launch and leaves
+ * y untouched.  Asynchronous, allocates nothing, safe under graph capture.
+ */
+int po2q_qconv2d_pair_bf16_supported(int64_t N, int64_t C, int64_t H, int64_t W, int bits, int fsr, int mode);
+size_t po2q_qconv2d_pair_bf16_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W,
+                                              int bits, int fsr, int mode);
+int po2q_qconv2d_pair_bf16(const uint16_t* x, const uint16_t* w1, const uint16_t* w2, uint16_t* y,
+                           int64_t N, int64_t C, int64_t H, int64_t W, int bits, int fsr, int mode,
+                           const uint16_t* bias1, const uint16_t* bias2,
+                           const float* post_scale1, const float* post_shift1, int act1,
+                           const float* post_scale2, const float* post_shift2, int add_x, int act2,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int po2q_qconv2d_pair_bf16_describe(int64_t N, int64_t C, int64_t H, int64_t W, int bits, int fsr, int mode,
+                                    char* buf, size_t len);
+
+/*
  * Kernel autotuning, the counterpart of the reference's
  * torch.backends.cudnn.benchmark = True (train.py:33, test.py:31): times every
  * candidate plan for this problem on these buffers (synchronises the stream;

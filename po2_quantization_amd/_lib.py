@@ -81,6 +81,10 @@ EXPORTS = (
     "po2q_bf16_row_kernels",
     "po2q_bf16_set_rowsk_kernels",
     "po2q_bf16_rowsk_kernels",
+    "po2q_qconv2d_pair_bf16_supported",
+    "po2q_qconv2d_pair_bf16_workspace_bytes",
+    "po2q_qconv2d_pair_bf16",
+    "po2q_qconv2d_pair_bf16_describe",
 )
 
 # Kernel autotuning on the first call per conv problem, the counterpart of
@@ -228,6 +232,15 @@ def load():
     L.po2q_bf16_set_rowsk_kernels.argtypes = [i32]
     L.po2q_bf16_rowsk_kernels.restype = i32
     L.po2q_bf16_rowsk_kernels.argtypes = []
+    L.po2q_qconv2d_pair_bf16_supported.restype = i32
+    L.po2q_qconv2d_pair_bf16_supported.argtypes = [i64] * 4 + [i32, i32, i32]
+    L.po2q_qconv2d_pair_bf16_workspace_bytes.restype = sz
+    L.po2q_qconv2d_pair_bf16_workspace_bytes.argtypes = [i64] * 4 + [i32, i32, i32]
+    L.po2q_qconv2d_pair_bf16.restype = i32
+    L.po2q_qconv2d_pair_bf16.argtypes = ([p, p, p, p] + [i64] * 4 + [i32, i32, i32, p, p, p, p, i32, p, p, i32, i32,
+                                                                        p, sz, p])
+    L.po2q_qconv2d_pair_bf16_describe.restype = i32
+    L.po2q_qconv2d_pair_bf16_describe.argtypes = [i64] * 4 + [i32, i32, i32, ctypes.c_char_p, sz]
     _lib = L
     return L
 
@@ -554,6 +567,71 @@ def describe_bf16(N, C, H, W, K, R, S, stride=1, padding=0, dilation=1, groups=1
     _check(L.po2q_qconv2d_bf16_describe(N, C, H, W, K, R, S, *_pair(stride), *_pair(padding), *_pair(dilation),
                                         int(groups), int(bits), int(fsr), MODES[mode], buf, 512))
     return buf.value.decode()
+
+
+def pair_bf16_supported(shape, bits=4, mode="po2", fsr=1):
+    """Whether qconv2d_pair_bf16 takes an input of this [N, C, H, W] shape (po2q_qconv2d_pair_bf16_supported:
+    C in {16, 32}, W even and <= 256 / 128, mode none / po2 / po2+).  Eligibility only, no speed advice."""
+    if len(shape) != 4 or mode not in MODES:
+        return False
+    return bool(load().po2q_qconv2d_pair_bf16_supported(*[int(v) for v in shape], int(bits), int(fsr), MODES[mode]))
+
+
+def describe_pair_bf16(N, C, H, W, bits=4, mode="po2", fsr=1):
+    """The plan qconv2d_pair_bf16 runs for this shape ("kind=bf16_pair C=.. RB=.. ..."; diagnostic text)."""
+    buf = ctypes.create_string_buffer(512)
+    _check(load().po2q_qconv2d_pair_bf16_describe(N, C, H, W, int(bits), int(fsr), MODES[mode], buf, 512))
+    return buf.value.decode()
+
+
+def qconv2d_pair_bf16(x, w1, w2, bias1=None, bias2=None, bits=4, mode="po2", fsr=1, post_scale1=None,
+                      post_shift1=None, act1="none", post_scale2=None, post_shift2=None, add_x=False, act2="none"):
+    """Both 3x3 / stride 1 / pad 1 convs of a bf16 BasicBlock with an identity shortcut in one launch
+    (po2q_qconv2d_pair_bf16), the intermediate kept on chip:
+        mid = bf16(act1((conv(x, Q(w1)) + bias1) * post_scale1 + post_shift1))
+        y   = bf16(act2((conv(mid, Q(w2)) + bias2) * post_scale2 + post_shift2 + x (add_x)))
+    i.e. two qconv2d_fused_bf16 calls with residual = x up to the accumulation order.  C in {16, 32}, W even
+    and <= 256 / 128 (pair_bf16_supported); anything else raises.  Forward only."""
+    _require_hip_bf16(x, "input")
+    if x.dim() != 4:
+        raise Po2qError("po2q: expected a 4-D input, got %d-D" % x.dim())
+    C = x.shape[1]
+    for w in (w1, w2):
+        _require_hip_bf16(w, "weight")
+        if tuple(w.shape) != (C, C, 3, 3) or w.device != x.device:
+            raise Po2qError("po2q: the bf16 conv pair takes [C, C, 3, 3] weights with C = %d on the input's device, "
+                            "got %s" % (C, list(w.shape)))
+    for b in (bias1, bias2):
+        if b is not None:
+            _require_hip_bf16(b, "bias")
+            if b.numel() != C or b.device != x.device:
+                raise Po2qError("po2q: bias must have %d elements on the input's device" % C)
+    ext1, _ = _bf16_epilogue(x, x.shape, post_scale1, post_shift1, None)
+    ext2, _ = _bf16_epilogue(x, x.shape, post_scale2, post_shift2, None)
+    mode_id = MODES[mode]
+    if x.shape[0] == 0:
+        return torch.empty_like(x, memory_format=torch.contiguous_format)
+    O = ops()
+    if O is not None:
+        return _op_call(O.qconv2d_pair_bf16, x, w1, w2, bias1, bias2, int(bits), mode_id, int(fsr), ext1[0], ext1[1],
+                        ACTS[act1], ext2[0], ext2[1], bool(add_x), ACTS[act2])
+    L = load()
+    xc, w1c, w2c = x.contiguous(), w1.contiguous(), w2.contiguous()
+    b1c = bias1.contiguous() if bias1 is not None else None
+    b2c = bias2.contiguous() if bias2 is not None else None
+    geo = [int(v) for v in xc.shape]
+    with torch.cuda.device(xc.device):
+        nbytes = L.po2q_qconv2d_pair_bf16_workspace_bytes(*geo, int(bits), int(fsr), mode_id)
+        if nbytes == 0:
+            _check(1)
+        y = torch.empty(xc.shape, dtype=torch.bfloat16, device=xc.device)
+        ws = _workspace(nbytes, xc.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        _check(L.po2q_qconv2d_pair_bf16(xc.data_ptr(), w1c.data_ptr(), w2c.data_ptr(), y.data_ptr(), *geo, int(bits),
+                                        int(fsr), mode_id, ptr(b1c), ptr(b2c), ptr(ext1[0]), ptr(ext1[1]), ACTS[act1],
+                                        ptr(ext2[0]), ptr(ext2[1]), 1 if add_x else 0, ACTS[act2], ws.data_ptr(),
+                                        ws.numel(), _stream(xc.device)))
+    return y
 
 
 def set_bf16_row_kernels(on):

@@ -749,6 +749,80 @@ int po2q_qconv2d_bf16_describe(int64_t N, int64_t C, int64_t H, int64_t W, int64
     return PO2Q_OK;
 }
 
+// ------------------------------------------------------------------ bf16 conv pair --
+// The checks the pair entries share: mode and bits, no lin mode, the geometry and the eligible shapes.
+static int b16_pair_resolve(B16PairPlan& p, int64_t N, int64_t C, int64_t H, int64_t W, int bits, int mode) {
+    if (!check_mode_bits(mode, bits, true)) return PO2Q_ERR_INVALID;
+    if (is_lin_mode(mode)) {
+        set_error("po2q: the bf16 conv pair has no lin / lin+ mode (there is no bf16 lin quantizer)");
+        return PO2Q_ERR_UNSUPPORTED;
+    }
+    return b16_pair_plan(p, N, C, H, W);
+}
+
+int po2q_qconv2d_pair_bf16_supported(int64_t N, int64_t C, int64_t H, int64_t W, int bits, int fsr, int mode) {
+    (void)fsr;
+    B16PairPlan p;
+    return b16_pair_resolve(p, N, C, H, W, bits, mode) == PO2Q_OK ? 1 : 0;
+}
+
+size_t po2q_qconv2d_pair_bf16_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int bits, int fsr,
+                                              int mode) {
+    (void)fsr;
+    B16PairPlan p;
+    if (b16_pair_resolve(p, N, C, H, W, bits, mode)) return 0;
+    return b16_pair_workspace_bytes(p);
+}
+
+int po2q_qconv2d_pair_bf16(const uint16_t* x, const uint16_t* w1, const uint16_t* w2, uint16_t* y, int64_t N,
+                           int64_t C, int64_t H, int64_t W, int bits, int fsr, int mode, const uint16_t* bias1,
+                           const uint16_t* bias2, const float* post_scale1, const float* post_shift1, int act1,
+                           const float* post_scale2, const float* post_shift2, int add_x, int act2, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    if (!check_mode_bits(mode, bits, true)) return PO2Q_ERR_INVALID;
+    if (!x || !w1 || !w2 || !y || !workspace) {
+        set_error("po2q: null pointer");
+        return PO2Q_ERR_INVALID;
+    }
+    if (x == y) {
+        set_error("po2q: the bf16 conv pair's y must not alias x");
+        return PO2Q_ERR_INVALID;
+    }
+    for (int act : {act1, act2})
+        if (act < PO2Q_ACT_NONE || act > PO2Q_ACT_SILU) {
+            set_error("po2q: unknown activation " + std::to_string(act));
+            return PO2Q_ERR_INVALID;
+        }
+    B16PairPlan p;
+    const int st = b16_pair_resolve(p, N, C, H, W, bits, mode);
+    if (st) return st;
+    const size_t need = b16_pair_workspace_bytes(p);
+    if (workspace_bytes < need) {
+        set_error("po2q: conv pair workspace too small (need " + std::to_string(need) + " bytes)");
+        return PO2Q_ERR_WORKSPACE;
+    }
+    B16Epi e1, e2;
+    e1.ps = post_scale1; e1.pb = post_shift1; e1.act = act1;
+    e2.ps = post_scale2; e2.pb = post_shift2; e2.act = act2;
+    return hip_status(b16_pair_run(p, x, w1, w2, y, bits, fsr, mode, bias1, bias2, e1, e2, add_x, workspace,
+                                   reinterpret_cast<hipStream_t>(stream)),
+                      "bf16 conv pair launch");
+}
+
+int po2q_qconv2d_pair_bf16_describe(int64_t N, int64_t C, int64_t H, int64_t W, int bits, int fsr, int mode,
+                                    char* buf, size_t len) {
+    (void)fsr;
+    if (!buf || len == 0) {
+        set_error("po2q: describe needs a buffer");
+        return PO2Q_ERR_INVALID;
+    }
+    B16PairPlan p;
+    const int st = b16_pair_resolve(p, N, C, H, W, bits, mode);
+    if (st) return st;
+    b16_pair_describe(p, buf, len);
+    return PO2Q_OK;
+}
+
 int po2q_bf16_set_row_kernels(int on) { return b16_rows_set(on); }
 
 int po2q_bf16_row_kernels(void) { return b16_rows_get(); }

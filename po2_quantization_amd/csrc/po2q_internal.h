@@ -337,6 +337,24 @@ void b16_rowsk_describe(const ConvPlan& p, char* buf, size_t len);
 hipError_t b16_rowsk_launch(const ConvPlan& p, const uint16_t* x, const uint16_t* packed, const uint16_t* bias,
                             uint16_t* y, hipStream_t s, const B16Epi& e);
 
+// bf16 BasicBlock conv pair (po2q_conv_b16p.hip; po2q_qconv2d_pair_bf16): both 3x3 / stride 1 / pad 1 convs
+// of an identity block in one launch, C = 16 or 32, W even and <= 256 / 128.  b16_pair_plan validates the
+// geometry and fills the plan (0, or the PO2Q_ERR_* code with the error set); it reads no switch.  `conv`
+// is the geometry of either conv in the row kernels' pack layout, which is what b16_pack_batch reads.
+// b16_pair_run enqueues the batched max|w| and pack launches of both weights and the pair kernel.
+struct B16PairPlan {
+    ConvPlan conv;
+    int GW, RB, bands, ngroups;  // groups per wave, rows per band, bands per image, 16-column groups per row
+    size_t lds_bytes;
+    int64_t blocks;
+};
+int b16_pair_plan(B16PairPlan& p, int64_t N, int64_t C, int64_t H, int64_t W);
+size_t b16_pair_workspace_bytes(const B16PairPlan& p);
+void b16_pair_describe(const B16PairPlan& p, char* buf, size_t len);
+hipError_t b16_pair_run(const B16PairPlan& p, const uint16_t* x, const uint16_t* w1, const uint16_t* w2, uint16_t* y,
+                        int bits, int fsr, int mode, const uint16_t* bias1, const uint16_t* bias2, const B16Epi& e1,
+                        const B16Epi& e2, int add_x, void* workspace, hipStream_t s);
+
 // lin / lin+ quantizer (po2q_lin.hip): w, out [d0, d1, rs = d2*d3], one block per d1 channel
 hipError_t launch_quantize_lin(const float* w, float* out, int d0, int d1, int rs, int bits, int num_iters, int plus,
                                hipStream_t s);

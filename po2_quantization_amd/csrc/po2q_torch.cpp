@@ -29,6 +29,7 @@
 //                        bf16, one bf16 MFMA pass (po2q_qconv2d_bf16); forward only
 //   po2q::qconv2d_fused_bf16  the same + eval BatchNorm affine (fp32), bf16 residual add and activation
 //                        in the conv kernel's store, one rounding to bf16 (po2q_qconv2d_fused_bf16)
+//   po2q::qconv2d_pair_bf16  both convs of a bf16 identity BasicBlock in one launch (po2q_qconv2d_pair_bf16)
 //   po2q::qconv2d_pack_batch_bf16 / po2q::qconv2d_packed_bf16  the bf16 forward's weight staging of many
 //                        layers as batched launches, and each conv (+ epilogue) from its pack
 // Meta kernels give the output shapes (FX / torch.compile tracing, fake tensors).
@@ -354,6 +355,66 @@ at::Tensor qconv2d_bf16_meta(const at::Tensor& x, const at::Tensor& w, const c10
                              at::IntArrayRef stride, at::IntArrayRef padding, at::IntArrayRef dilation, int64_t,
                              int64_t, int64_t, int64_t) {
     return at::empty(conv_out_shape(x, w, stride, padding, dilation), x.options().dtype(at::kBFloat16));
+}
+
+// ---- bf16 BasicBlock conv pair (po2q_qconv2d_pair_bf16): both convs of an identity block in one launch ----
+at::Tensor qconv2d_pair_bf16(const at::Tensor& x_, const at::Tensor& w1_, const at::Tensor& w2_,
+                             const c10::optional<at::Tensor>& bias1_, const c10::optional<at::Tensor>& bias2_,
+                             int64_t bits, int64_t mode, int64_t fsr, const c10::optional<at::Tensor>& ps1_,
+                             const c10::optional<at::Tensor>& pb1_, int64_t act1,
+                             const c10::optional<at::Tensor>& ps2_, const c10::optional<at::Tensor>& pb2_,
+                             bool add_x, int64_t act2) {
+    check_hip_bf16(x_, "input");
+    check_hip_bf16(w1_, "weight 1");
+    check_hip_bf16(w2_, "weight 2");
+    TORCH_CHECK(x_.dim() == 4, "po2q: expected a 4-D input, got ", x_.dim(), "-D");
+    const int64_t C = x_.size(1);
+    for (const at::Tensor* w : {&w1_, &w2_}) {
+        TORCH_CHECK(w->device() == x_.device(), "po2q: input and weights must be on the same device");
+        TORCH_CHECK(w->dim() == 4 && w->size(0) == C && w->size(1) == C && w->size(2) == 3 && w->size(3) == 3,
+                    "po2q: the bf16 conv pair takes [C, C, 3, 3] weights with C = ", C, ", got ", w->sizes());
+    }
+    TORCH_CHECK(act1 >= 0 && act1 <= 3 && act2 >= 0 && act2 <= 3, "po2q: unknown activation ", act1, " / ", act2);
+    c10::optional<at::Tensor> b1, b2, ps1, pb1, ps2, pb2;
+    for (auto [src, dst] : {std::make_pair(&bias1_, &b1), std::make_pair(&bias2_, &b2)}) {
+        if (!src->has_value()) continue;
+        check_hip_bf16(**src, "bias");
+        TORCH_CHECK((*src)->device() == x_.device() && (*src)->numel() == C, "po2q: bias must have ", C,
+                    " elements on the input's device");
+        *dst = (*src)->contiguous();
+    }
+    for (auto [src, dst] : {std::make_pair(&ps1_, &ps1), std::make_pair(&pb1_, &pb1), std::make_pair(&ps2_, &ps2),
+                            std::make_pair(&pb2_, &pb2)}) {
+        if (!src->has_value()) continue;
+        check_hip_f32(**src, "post_scale / post_shift");
+        TORCH_CHECK((*src)->device() == x_.device() && (*src)->numel() == C, "po2q: post_scale / post_shift must have ",
+                    C, " elements on the input's device");
+        *dst = (*src)->contiguous();
+    }
+    const DeviceGuard guard(x_.device());
+    const at::Tensor x = x_.contiguous(), w1 = w1_.contiguous(), w2 = w2_.contiguous();
+    at::Tensor y = at::empty(x.sizes(), x.options());
+    if (x.size(0) == 0) return y;
+    const size_t wsb = po2q_qconv2d_pair_bf16_workspace_bytes(x.size(0), C, x.size(2), x.size(3), (int)bits, (int)fsr,
+                                                              (int)mode);
+    TORCH_CHECK(wsb > 0, last_error());
+    at::Tensor ws = at::empty({(int64_t)wsb}, x.options().dtype(at::kByte));
+    auto ptr = [](const at::Tensor& t) { return reinterpret_cast<uint16_t*>(t.data_ptr()); };
+    const int st = po2q_qconv2d_pair_bf16(ptr(x), ptr(w1), ptr(w2), ptr(y), x.size(0), C, x.size(2), x.size(3), (int)bits,
+                                          (int)fsr, (int)mode, b1.has_value() ? ptr(*b1) : nullptr,
+                                          b2.has_value() ? ptr(*b2) : nullptr, opt_ptr(ps1), opt_ptr(pb1), (int)act1,
+                                          opt_ptr(ps2), opt_ptr(pb2), add_x ? 1 : 0, (int)act2, ws.data_ptr(), wsb,
+                                          stream_of(x));
+    TORCH_CHECK(st == 0, last_error());
+    return y;
+}
+
+at::Tensor qconv2d_pair_bf16_meta(const at::Tensor& x, const at::Tensor&, const at::Tensor&,
+                                  const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&, int64_t, int64_t,
+                                  int64_t, const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&, int64_t,
+                                  const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&, bool, int64_t) {
+    TORCH_CHECK(x.dim() == 4, "po2q: expected a 4-D input, got ", x.dim(), "-D");
+    return at::empty(x.sizes(), x.options().dtype(at::kBFloat16));
 }
 
 // ---- batched weight staging of the bf16 forward (po2q_qconv2d_bf16_pack_batch / _packed_bf16) ----
@@ -1063,6 +1124,9 @@ TORCH_LIBRARY(po2q, m) {
     m.def("qconv2d_packed_bf16(Tensor x, Tensor w, Tensor workspace, Tensor? bias, int[] stride, int[] padding, "
           "int[] dilation, int groups, int bits, int mode, int fsr=1, Tensor? post_scale=None, "
           "Tensor? post_shift=None, Tensor? residual=None, int act=0) -> Tensor");
+    m.def("qconv2d_pair_bf16(Tensor x, Tensor w1, Tensor w2, Tensor? bias1, Tensor? bias2, int bits, int mode, "
+          "int fsr=1, Tensor? post_scale1=None, Tensor? post_shift1=None, int act1=0, Tensor? post_scale2=None, "
+          "Tensor? post_shift2=None, bool add_x=False, int act2=0) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(po2q, CUDA, m) {  // the HIP device (PyTorch-ROCm dispatches HIP tensors under CUDA)
@@ -1082,6 +1146,7 @@ TORCH_LIBRARY_IMPL(po2q, CUDA, m) {  // the HIP device (PyTorch-ROCm dispatches 
     m.impl("qconv2d_fused_bf16", &qconv2d_fused_bf16);
     m.impl("qconv2d_pack_batch_bf16", &qconv2d_pack_batch_bf16);
     m.impl("qconv2d_packed_bf16", &qconv2d_packed_bf16);
+    m.impl("qconv2d_pair_bf16", &qconv2d_pair_bf16);
 }
 
 TORCH_LIBRARY_IMPL(po2q, Meta, m) {
@@ -1101,4 +1166,5 @@ TORCH_LIBRARY_IMPL(po2q, Meta, m) {
     m.impl("qconv2d_fused_bf16", &qconv2d_fused_bf16_meta);
     m.impl("qconv2d_pack_batch_bf16", &qconv2d_pack_batch_bf16_meta);
     m.impl("qconv2d_packed_bf16", &qconv2d_packed_bf16_meta);
+    m.impl("qconv2d_pair_bf16", &qconv2d_pair_bf16_meta);
 }

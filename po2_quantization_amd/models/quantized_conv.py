@@ -237,11 +237,21 @@ INFERENCE_FUSION = True
 # conv, after the BatchNorm and after the add, so the fused result is closer to the exact one but not
 # the sequence's bits (tools/bf16_conv_bench.py --fused times both sides).
 BF16_FUSED_EPILOGUE = False
+# With BF16_FUSED_EPILOGUE: a BasicBlock with an identity shortcut and 16 or 32 channels on a bf16 input runs
+# both of its convs as ONE launch, the intermediate kept on chip (po2q_qconv2d_pair_bf16; models/resnet.py).
+# Opt-in, and without effect while BF16_FUSED_EPILOGUE is off.  The result is the two fused bf16 calls' up to the
+# accumulation order.
+BF16_PAIRS = False
 
 
 def bf16_fused_input(x):
     """True when the fused calls take this input to the fused bf16 entry (BF16_FUSED_EPILOGUE)."""
     return BF16_FUSED_EPILOGUE and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
+
+
+def bf16_pair_input(x):
+    """True when an eligible BasicBlock takes this input to the bf16 conv pair (both switches on)."""
+    return BF16_PAIRS and bf16_fused_input(x)
 
 
 def _has_hooks(conv):
@@ -383,7 +393,8 @@ def _record_key(model, x):
     kernels' weight layouts differ)."""
     rows = (_lib.bf16_row_kernels(), _lib.bf16_rowsk_kernels())
     if x.dtype == torch.bfloat16:
-        return (tuple(x.shape), x.device, x.dtype, BF16_FUSED_EPILOGUE, INFERENCE_FUSION, rows)
+        # (and BF16_PAIRS: a pair block's layers stage their own weights and are not in the record)
+        return (tuple(x.shape), x.device, x.dtype, BF16_FUSED_EPILOGUE, INFERENCE_FUSION, rows, BF16_PAIRS)
     # the record holds which layers read a packed weight and with which plan; it depends on the
     # layers' quantizer settings and precision as much as on the input shape
     confs = tuple((m.bits, native_mode(m.quantize_fn), m.precision) for m in model.modules()

@@ -19,8 +19,8 @@ import torch.nn as nn
 
 from .. import _lib
 from ..utils.quantizers import NATIVE_MODES
-from .quantized_conv import (QuantizedConv2d, batched_packs, bf16_fused_input, can_fuse, fold_bn, plain_conv,
-                             plain_conv_fused, run_fused_sequence)
+from .quantized_conv import (QuantizedConv2d, _has_hooks, batched_packs, bf16_fused_input, bf16_pair_input, can_fuse,
+                             fold_bn, fold_bn_f32, plain_conv, plain_conv_fused, run_fused_sequence)
 
 
 class BasicBlock(nn.Module):
@@ -48,6 +48,15 @@ class BasicBlock(nn.Module):
                 return _lib.qconv2d_pair(x, self.conv1.weight, self.conv2.weight, self.conv1.bits,
                                          NATIVE_MODES[self.conv1.quantize_fn], post_scale1=ps1, post_shift1=pb1,
                                          act1="relu", post_scale2=ps2, post_shift2=pb2, residual=x, act2="relu")
+            if self._pair_bf16_ok(x):
+                # the same block on a bf16 input (BF16_FUSED_EPILOGUE and BF16_PAIRS): po2q_qconv2d_pair_bf16,
+                # the BatchNorms folded in fp32
+                ps1, pb1 = fold_bn_f32(self.bn1)
+                ps2, pb2 = fold_bn_f32(self.bn2)
+                return _lib.qconv2d_pair_bf16(x, self.conv1.weight, self.conv2.weight, self.conv1.bias, self.conv2.bias,
+                                              self.conv1.bits, NATIVE_MODES[self.conv1.quantize_fn], 1, post_scale1=ps1,
+                                              post_shift1=pb1, act1="relu", post_scale2=ps2, post_shift2=pb2,
+                                              add_x=True, act2="relu")
             if self._s2ds_ok(x):
                 # conv1 -> bn1 -> relu and downsample (1x1 conv -> bn) on ONE read of x
                 # (po2q_qconv2d_s2ds_f32), then conv2 -> bn2 -> + shortcut -> relu
@@ -79,6 +88,21 @@ class BasicBlock(nn.Module):
                 and c2.precision != "fp32" and c1.bias is None and c2.bias is None
                 and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
                 and _lib.pair_supported(x.shape, c1.bits, mode))
+
+    def _pair_bf16_ok(self, x):
+        """_pair_ok for a bf16 input: the geometry, quantizer and bits conditions of the fp32 pair, both bf16
+        switches on, no forward hooks owed a conv's own output, and a shape the bf16 pair kernel takes."""
+        if not bf16_pair_input(x):
+            return False
+        c1, c2 = self.conv1, self.conv2
+        mode = NATIVE_MODES.get(c1.quantize_fn)
+        geom = all(tuple(c.kernel_size) == (3, 3) and tuple(c.stride) == (1, 1) and tuple(c.padding) == (1, 1)
+                   and tuple(c.dilation) == (1, 1) and c.groups == 1 and c.padding_mode == "zeros" for c in (c1, c2))
+        return (self.downsample is None and geom and mode in ("po2", "po2+") and c2.quantize_fn is c1.quantize_fn
+                and c1.bits == c2.bits and c1.in_channels in (16, 32) and c1.out_channels == c1.in_channels
+                and c2.in_channels == c1.in_channels and c2.out_channels == c1.in_channels
+                and x.shape[1] == c1.in_channels and not _has_hooks(c1) and not _has_hooks(c2)
+                and _lib.pair_bf16_supported(x.shape, c1.bits, mode))
 
     def _s2ds_ok(self, x):
         """conv1 (3x3 stride 2, C -> 2C) and the projection shortcut (QuantizedConv2d 1x1 stride 2 +

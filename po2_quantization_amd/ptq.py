@@ -150,10 +150,11 @@ def tensor_loader(data_file: str, batch_size: int):
 def main(model_type: str, dataset: str, data_file: str, batch_size: int = 128, train_dir: str = "./train",
          results_dir: str = "./results", skip_qat: bool = False, dtype: str = "fp32",
          bf16_fused_epilogue: bool = False, bf16_row_kernels: bool = False,
-         bf16_rowsk_kernels: bool = False) -> None:
+         bf16_rowsk_kernels: bool = False, bf16_pairs: bool = False) -> None:
     """test.py:58-164 with the evaluation set from data_file."""
     assert dtype in DTYPES, "invalid dtype"
     assert not bf16_fused_epilogue or dtype == "bf16", "--bf16-fused-epilogue needs --dtype bf16"
+    assert not bf16_pairs or bf16_fused_epilogue, "--bf16-pairs needs --dtype bf16 --bf16-fused-epilogue"
     assert not bf16_row_kernels or dtype == "bf16", "--bf16-row-kernels needs --dtype bf16"
     assert not bf16_rowsk_kernels or dtype == "bf16", "--bf16-rowsk-kernels needs --dtype bf16"
     assert torch.cuda.is_available(), "invalid hardware"
@@ -170,6 +171,8 @@ def main(model_type: str, dataset: str, data_file: str, batch_size: int = 128, t
     Path(results_work_dir).mkdir(parents=True, exist_ok=True)
     saved = quantized_conv.BF16_FUSED_EPILOGUE
     quantized_conv.BF16_FUSED_EPILOGUE = bool(bf16_fused_epilogue)  # for this run
+    saved_pairs = quantized_conv.BF16_PAIRS
+    quantized_conv.BF16_PAIRS = bool(bf16_pairs)  # for this run
     saved_rows = _lib.set_bf16_row_kernels(bool(bf16_row_kernels))  # for this run
     saved_rowsk = _lib.set_bf16_rowsk_kernels(bool(bf16_rowsk_kernels))  # for this run
     try:
@@ -180,6 +183,7 @@ def main(model_type: str, dataset: str, data_file: str, batch_size: int = 128, t
             write_results(f"{results_work_dir}/{seed}.csv", rows)
     finally:
         quantized_conv.BF16_FUSED_EPILOGUE = saved
+        quantized_conv.BF16_PAIRS = saved_pairs
         _lib.set_bf16_row_kernels(saved_rows)
         _lib.set_bf16_rowsk_kernels(saved_rowsk)
 
@@ -200,6 +204,9 @@ def arg_parser():
     ap.add_argument("--bf16-fused-epilogue", action="store_true",
                     help="with --dtype bf16: BatchNorm, residual and activation in the conv kernel's store "
                          "(models.quantized_conv.BF16_FUSED_EPILOGUE), one rounding to bf16 per layer")
+    ap.add_argument("--bf16-pairs", action="store_true",
+                    help="with --dtype bf16 --bf16-fused-epilogue: both convs of an identity BasicBlock with 16 or 32 "
+                         "channels as one launch (models.quantized_conv.BF16_PAIRS)")
     ap.add_argument("--bf16-row-kernels", action="store_true",
                     help="with --dtype bf16: the row-streaming conv kernel for the 3x3 stride-1 C = K = 16 / 32 "
                          "layers (_lib.set_bf16_row_kernels), for this run")
@@ -212,4 +219,4 @@ def arg_parser():
 if __name__ == "__main__":
     a = arg_parser().parse_args()
     main(a.model_type, a.dataset, a.data_file, a.batch_size, a.train_dir, a.results_dir, a.skip_qat, a.dtype,
-         a.bf16_fused_epilogue, a.bf16_row_kernels, a.bf16_rowsk_kernels)
+         a.bf16_fused_epilogue, a.bf16_row_kernels, a.bf16_rowsk_kernels, a.bf16_pairs)

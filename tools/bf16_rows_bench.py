@@ -16,6 +16,11 @@ same with a residual added before the ReLU.  Every (layer, form) is timed --runs
 between two runs' medians of one arm), the bf16 bytes' fraction of the 8 TB/s HBM roof at the row arm's
 median, and whether the row arm's worst median is below the tile arm's best by more than the spread.
 
+--pair times the conv pair instead (po2q_qconv2d_pair_bf16, "kind=bf16_pair"), into profiles/bf16_pair.jsonl: one
+_lib.qconv2d_pair_bf16 call against the two _lib.qconv2d_fused_bf16 calls it replaces (both row-kernel switches
+on), in the forms plain (no BatchNorm, no activation, no shortcut) and bn+relu -> bn+add+relu; the roof fraction
+is that of the two activation passes a block needs (read x, write y) at each arm's worst median.
+
 Needs a GPU; there is no fallback."""
 import argparse
 import json
@@ -36,9 +41,68 @@ LAYERS = "16@224,32@112"  # C = K @ H = W; --layers 64@56 for stage 3
 FORMS = ["plain", "bn+relu", "bn+add+relu"]
 
 
+def pair_main(a, shapes):
+    dev = torch.device("cuda:0")
+    N = a.batch
+    lines = []
+    for C, H in shapes:
+        torch.manual_seed(0)
+        x = torch.randn(N, C, H, H, device=dev).to(torch.bfloat16)
+        w1, w2 = ((torch.randn(C, C, 3, 3, device=dev) * 0.1).to(torch.bfloat16) for _ in range(2))
+        folds = []
+        for _ in range(2):
+            bn = torch.nn.BatchNorm2d(C)
+            with torch.no_grad():
+                bn.running_mean.normal_()
+                bn.running_var.uniform_(0.5, 2.0)
+                bn.weight.normal_()
+                bn.bias.normal_()
+            folds.append(fold_bn_f32(bn.to(dev).eval()))
+        for form in ("plain", "bn+relu -> bn+add+relu"):
+            full = form != "plain"
+            (s1, t1), (s2, t2) = folds if full else ((None, None), (None, None))
+            act = "relu" if full else "none"
+
+            def two_calls():
+                with _lib.bf16_rows(True), _lib.bf16_rowsk(True):
+                    mid = _lib.qconv2d_fused_bf16(x, w1, None, 1, 1, 1, 1, a.bits, "po2", 1, post_scale=s1, post_shift=t1,
+                                                  act=act)
+                    return _lib.qconv2d_fused_bf16(mid, w2, None, 1, 1, 1, 1, a.bits, "po2", 1, post_scale=s2,
+                                                   post_shift=t2, residual=x if full else None, act=act)
+
+            def pair():
+                return _lib.qconv2d_pair_bf16(x, w1, w2, None, None, a.bits, "po2", 1, post_scale1=s1, post_shift1=t1,
+                                              act1=act, post_scale2=s2, post_shift2=t2, add_x=full, act2=act)
+
+            differ = float((two_calls() != pair()).float().mean())
+            arms = {"two_calls": two_calls, "pair": pair}
+            runs = [time_arms(arms, a.warmup, a.reps) for _ in range(a.runs)]
+            nbytes = 2 * N * C * H * H * 2
+            out = {"shape": [N, C, H, H], "bits": a.bits, "mode": "po2", "form": form, "reps": a.reps, "runs": a.runs,
+                   "needed_bytes": nbytes, "elements_differing": differ}
+            spread = 0.0
+            for name in arms:
+                meds = [round(statistics.median(ts[name]), 1) for ts in runs]
+                out[name + "_us_median"] = meds
+                out[name + "_us_min"] = [round(min(ts[name]), 1) for ts in runs]
+                out[name + "_hbm_roof_fraction"] = round(nbytes / HBM_BYTES_PER_S / (max(meds) * 1e-6), 3)
+                spread = max(spread, max(meds) - min(meds))
+            out["spread_us"] = round(spread, 1)
+            out["two_calls_over_pair_time"] = round(min(out["two_calls_us_median"]) / max(out["pair_us_median"]), 3)
+            out["pair_beats_two_calls_by_more_than_spread"] = bool(
+                min(out["two_calls_us_median"]) - max(out["pair_us_median"]) > spread)
+            out["pair_plan"] = _lib.describe_pair_bf16(N, C, H, H, a.bits, "po2")
+            lines.append(json.dumps(out))
+            print(lines[-1], flush=True)
+        del x
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bf16_rows.jsonl"))
+    ap.add_argument("--out", default=None, help="default: profiles/bf16_rows.jsonl (--pair: profiles/bf16_pair.jsonl)")
+    ap.add_argument("--pair", action="store_true", help="time the conv pair against the two fused calls it replaces")
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=256)
@@ -46,14 +110,15 @@ def main():
     ap.add_argument("--runs", type=int, default=2)
     ap.add_argument("--layers", default=LAYERS, help="comma-separated C@H layers (C = K, H = W)")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "bf16_pair.jsonl" if a.pair else "bf16_rows.jsonl")
     shapes = [tuple(int(v) for v in item.split("@")) for item in a.layers.split(",")]
     if not torch.cuda.is_available():
         raise SystemExit("bf16_rows_bench: no HIP device (timings are taken on the GPU only)")
     dev = torch.device("cuda:0")
     _lib.benchmark = True  # the fp32 entry autotunes on its first call
     N = a.batch
-    lines = []
-    for C, H in shapes:
+    lines = pair_main(a, shapes) if a.pair else []
+    for C, H in ([] if a.pair else shapes):
         torch.manual_seed(0)
         x32 = torch.randn(N, C, H, H, device=dev)
         w32 = torch.randn(C, C, 3, 3, device=dev) * 0.1

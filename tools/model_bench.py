@@ -7,7 +7,7 @@ Synthetic NCHW input, random-init weights (seeded), eval mode, torch.no_grad().
 "fused": conv+BN(+add)+act as one native call per conv; "unfused": the reference's
 module sequence (native conv, torch BatchNorm / ReLU / add).  GPU only.
 
-    python tools/model_bench.py --dtype bf16 [--bf16-row-kernels --bf16-rowsk-kernels --bf16-fused-epilogue]
+    python tools/model_bench.py --dtype bf16 [--bf16-row-kernels --bf16-rowsk-kernels --bf16-fused-epilogue --bf16-pairs]
                                 [--steps 20 --warmup 5 --runs 2]
 
 The bf16 forward (model.bfloat16(), bf16 input) in four arms: both row-kernel switches off, the first on,
@@ -43,22 +43,26 @@ def timed(fn, steps, warmup):
     return (time.perf_counter() - t0) / steps
 
 
-BF16_ARMS = {  # name -> (first switch, C = 64 switch, fused epilogue)
-    "off": (False, False, False),
-    "rows": (True, False, False),
-    "rows+rowsk": (True, True, False),
-    "rows+rowsk+fused": (True, True, True),
+BF16_ARMS = {  # name -> (first switch, C = 64 switch, fused epilogue, conv pairs)
+    "off": (False, False, False, False),
+    "rows": (True, False, False, False),
+    "rows+rowsk": (True, True, False, False),
+    "rows+rowsk+fused": (True, True, True, False),
+    "rows+rowsk+fused+pairs": (True, True, True, True),
 }
 
 
 def bf16_arms(args):
-    """The arms the flags name, beside the both-off arm; no flag: all four."""
-    if not (args.bf16_row_kernels or args.bf16_rowsk_kernels or args.bf16_fused_epilogue):
+    """The arms the flags name, beside the both-off arm; no flag: all five.  --bf16-pairs also times the named
+    arm without the pairs: that arm is what the pairs are compared with."""
+    if not (args.bf16_row_kernels or args.bf16_rowsk_kernels or args.bf16_fused_epilogue or args.bf16_pairs):
         return dict(BF16_ARMS)
-    name = "+".join(n for n, on in (("rows", args.bf16_row_kernels), ("rowsk", args.bf16_rowsk_kernels),
-                                    ("fused", args.bf16_fused_epilogue)) if on)
-    return {"off": BF16_ARMS["off"],
-            name: (args.bf16_row_kernels, args.bf16_rowsk_kernels, args.bf16_fused_epilogue)}
+    base = (args.bf16_row_kernels, args.bf16_rowsk_kernels, args.bf16_fused_epilogue)
+    name = "+".join(n for n, on in zip(("rows", "rowsk", "fused"), base) if on)
+    arms = {"off": BF16_ARMS["off"], name or "off": base + (False,)}
+    if args.bf16_pairs:
+        arms[(name + "+" if name else "") + "pairs"] = base + (True,)
+    return arms
 
 
 def bench_bf16(args):
@@ -68,11 +72,11 @@ def bench_bf16(args):
                   (args.image, args.image)).to(dev).eval().bfloat16()
     x = torch.randn(args.batch, 3, args.image, args.image, device=dev).to(torch.bfloat16)
     arms = bf16_arms(args)
-    saved = quantized_conv.BF16_FUSED_EPILOGUE
+    saved = quantized_conv.BF16_FUSED_EPILOGUE, quantized_conv.BF16_PAIRS
 
     def forward(setting):
-        first, new, fused = setting
-        quantized_conv.BF16_FUSED_EPILOGUE = fused
+        first, new, fused, pairs = setting
+        quantized_conv.BF16_FUSED_EPILOGUE, quantized_conv.BF16_PAIRS = fused, pairs
         with _lib.bf16_rows(first), _lib.bf16_rowsk(new):
             return m(x)
 
@@ -101,7 +105,7 @@ def bench_bf16(args):
                 res[name + "_logits_vs_off_normwise"] = float((forward(setting).float() - off).abs().max() / off.abs().max())
             res["spread_ms"] = round(max(max(v) - min(v) for v in meds.values()), 3)
     finally:
-        quantized_conv.BF16_FUSED_EPILOGUE = saved
+        quantized_conv.BF16_FUSED_EPILOGUE, quantized_conv.BF16_PAIRS = saved
     print(json.dumps(res), flush=True)
 
 
@@ -125,11 +129,13 @@ def main():
     ap.add_argument("--bf16-row-kernels", action="store_true", help="with --dtype bf16: time the arm with the C = 16 / 32 row kernel")
     ap.add_argument("--bf16-rowsk-kernels", action="store_true", help="with --dtype bf16: ... with the C = 64 row kernel")
     ap.add_argument("--bf16-fused-epilogue", action="store_true", help="with --dtype bf16: ... with the fused epilogue")
+    ap.add_argument("--bf16-pairs", action="store_true",
+                    help="with --dtype bf16 --bf16-fused-epilogue: ... with the identity blocks as conv pairs")
     ap.add_argument("--runs", type=int, default=2, help="with --dtype bf16: timed runs (the spread is between their medians)")
     args = ap.parse_args()
     if args.dtype == "bf16":
         return bench_bf16(args)
-    if args.bf16_row_kernels or args.bf16_rowsk_kernels or args.bf16_fused_epilogue:
+    if args.bf16_row_kernels or args.bf16_rowsk_kernels or args.bf16_fused_epilogue or args.bf16_pairs:
         ap.error("the --bf16-* options need --dtype bf16")
     if args.ir or args.no_ir:
         quantized_conv.IR_FUSION = bool(args.ir)
