@@ -62,9 +62,6 @@ struct B16Args {
     int vec;      // 8-byte epilogue stores possible (TQ % 4 == 0)
 };
 
-// (a & 0xffff) | (b << 16): the low bf16 halves of a (low) and b (high) as one dword
-__device__ __forceinline__ uint32_t pk_lo16(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); }
-
 // The fused epilogue on a lane's 4 values: v * sk + tk (when aff), + residual (when has), activation
 template <int ACT>
 __device__ __forceinline__ void b16_epi4(float (&v)[4], bool aff, float sk, float tk, bool has,
@@ -634,9 +631,8 @@ int b16_plan(ConvPlan& p) {
 }
 
 // Workspace: [max|w| partials, 256 B aligned][packed weight]
-size_t b16_workspace_bytes(const ConvPlan& p) {
-    return align256((size_t)kB16Parts * sizeof(uint32_t)) + align256((size_t)p.packed_floats * 4);
-}
+size_t b16_packed_offset() { return align256((size_t)kB16Parts * sizeof(uint32_t)); }
+size_t b16_workspace_bytes(const ConvPlan& p) { return b16_packed_offset() + align256((size_t)p.packed_floats * 4); }
 
 void b16_describe(const ConvPlan& p, char* buf, size_t len) {
     if (p.kind == KIND_BF16_ROWSK)
@@ -656,7 +652,7 @@ void b16_describe(const ConvPlan& p, char* buf, size_t len) {
 namespace {
 
 uint16_t* b16_packed_ptr(void* workspace) {
-    return reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(workspace) + align256((size_t)kB16Parts * sizeof(uint32_t)));
+    return reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(workspace) + b16_packed_offset());
 }
 
 // what the quantize + pack of one weight tensor is told: the plan's fragment layout and the window

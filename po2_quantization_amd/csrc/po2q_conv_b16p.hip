@@ -7,7 +7,8 @@
 // Q(w) comes from the shared quant_bf16 body through pack_b16 (row layout [tap row][k-step][nt][lane][8]),
 // one v_mfma_f32_16x16x32_bf16 per k-step, fp32 accumulation, one rounding per value.
 //
-// Walk: conv_b16_rows' (po2q_conv_b16r.hip) with the fp32 pairs' role split.
+// Walk: conv_b16_rows' (po2q_conv_b16r.hip) with the fp32 pairs' role split; staging, zero slot and stores are
+// po2q_b16_rows_dev.h's and are described there.
 //   * one 512-thread block owns (image, band of RB output rows) across the whole width.  Waves 0 - 3 are
 //     conv-1 waves, waves 4 - 7 conv-2 waves: one of each role on every SIMD.  Within a role the 16-column
 //     pixel groups are dealt as in conv_b16_rows, GW consecutive groups per wave;
@@ -32,33 +33,25 @@
 //     slots are written once, as zeros; conv-1 lanes past the row end write nothing;
 //   * a band computes the mid rows p0 - 1 and p0 + RB it shares with its neighbours itself; tap rows whose
 //     output row the band does not want are skipped (wave-uniform);
-//   * stores: conv_b16_rows' (16-byte pieces, 4-byte and 2-byte fallbacks by alignment); x staging with dword
-//     loads only when x is 4-byte aligned.
+//   * the residual is x itself and never comes from HBM a second time: a lane picks it out of the x ring.
 // LDS: 6 planes of (W + 2) * 2C + 16 bytes, 4 tiles of C * (32 GW + 16) bytes and conv 1's 12 C bytes of
 // epilogue parameters.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdio>
 #include <string>
 
-#include "po2q_epi.h"
-#include "po2q_internal.h"
-#include "po2q_quant_b16_dev.h"
-#include "po2q_x3_dev.h"
+#include "po2q_b16_rows_dev.h"
 
 namespace po2q {
 
 namespace {
 
-constexpr int kPThreads = 512;   // 4 conv-1 waves + 4 conv-2 waves
-constexpr int kPRole = 4;        // waves per role
+constexpr int kPThreads = 512;        // 4 conv-1 waves + 4 conv-2 waves
+constexpr int kPRole = kB16RowWaves;  // waves per role
 constexpr int kPXRing = 4, kPMRing = 2;
 
-constexpr int pair_ks(int C) { return C == 16 ? 2 : 3; }
-constexpr int pair_tpitch(int GW) { return GW * 32 + 16; }
-int pair_plane(int C, int W) { return (W + 2) * 2 * C + 16; }  // + the zero slot
-int pair_wmax(int C) { return C == 16 ? 256 : 128; }           // one staging item per conv-1 thread
+int pair_wmax(int C) { return C == 16 ? 256 : 128; }  // one staging item per conv-1 thread
 
 struct B16PArgs {
     int H, W;
@@ -70,8 +63,6 @@ struct B16PArgs {
     const float *ps1, *pb1, *ps2, *pb2;
 };
 
-__device__ __forceinline__ uint32_t ppk_lo16(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); }
-
 template <int C, int GW>
 __global__ __launch_bounds__(kPThreads) void conv_b16_pair(const uint16_t* __restrict__ x,
                                                            const uint4* __restrict__ wpk1,
@@ -79,8 +70,8 @@ __global__ __launch_bounds__(kPThreads) void conv_b16_pair(const uint16_t* __res
                                                            uint16_t* __restrict__ y, B16PArgs a) {
     static_assert(C == 16 || C == 32, "C = 16 or 32");
     static_assert(GW == 1 || GW == 2 || GW == 4, "groups per wave");
-    constexpr int NT = C / 16, KS = pair_ks(C), OCT = C / 8;
-    constexpr int TP = pair_tpitch(GW);
+    constexpr int NT = C / 16, KS = b16_rows_ks(C);
+    constexpr int TP = b16_rows_tpitch(GW);
     constexpr int CH = GW * 2;  // 16-byte pieces per channel of the transpose tile
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -102,12 +93,7 @@ __global__ __launch_bounds__(kPThreads) void conv_b16_pair(const uint16_t* __res
     unsigned char* tile = lds + (kPXRing + kPMRing) * PL + rw * (C * TP);  // conv-2 waves
     const int zero_off = (W + 2) * 2 * C;
 
-    // ---- zeros, once: halo columns 0 and W + 1 and the zero slot of every plane
-    if (tid < (kPXRing + kPMRing) * (2 * OCT + 1)) {
-        const int pl = tid / (2 * OCT + 1), r = tid - pl * (2 * OCT + 1);
-        const int off = r == 2 * OCT ? zero_off : x_addr<C>(r < OCT ? 0 : W + 1, r % OCT);
-        *reinterpret_cast<uint4*>(lds + pl * PL + off) = make_uint4(0u, 0u, 0u, 0u);
-    }
+    zero_planes<C, true>(lds, kPXRing + kPMRing, PL, W, zero_off, tid);
 
     // ---- this role's weight fragments [tap row][k-step][nt], resident
     const uint4* wpk = conv2 ? wpk2 : wpk1;
@@ -125,39 +111,21 @@ __global__ __launch_bounds__(kPThreads) void conv_b16_pair(const uint16_t* __res
     for (int g = 0; g < GW; ++g) {
         const int q = min((rw * GW + g) * 16 + (lane & 15), W - 1);  // ragged / idle groups: a column inside
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            if constexpr (C == 16)
-                aoff[g][ks] = ks == 0 ? x_addr<16>(q + (o >> 1), o & 1) : (o < 2 ? x_addr<16>(q + 2, o) : zero_off);
-            else
-                aoff[g][ks] = x_addr<32>(q + ks, o);
-        }
+        for (int ks = 0; ks < KS; ++ks) aoff[g][ks] = frag_off<C>(q, ks, o, zero_off);
     }
 
     // ---- staging (conv-1 waves): one (channel octet, pixel pair) item per thread
     const int W2 = W >> 1;
-    const bool sv = !conv2 && tid < OCT * W2;
-    const int soc = sv ? tid / W2 : 0, sm = sv ? tid - soc * W2 : 0;
-    const int64_t sg = (int64_t)(soc * 8) * HW + 2 * sm;
-    const int sl0 = x_addr<C>(2 * sm + 1, soc), sl1 = x_addr<C>(2 * sm + 2, soc);
+    B16Stage st;
+    st.v = !conv2 && tid < C / 8 * W2;
+    const int soc = st.v ? tid / W2 : 0, sm = st.v ? tid - soc * W2 : 0;
+    st.g = (int64_t)(soc * 8) * HW + 2 * sm;
+    st.l0 = x_addr<C>(2 * sm + 1, soc);
+    st.l1 = x_addr<C>(2 * sm + 2, soc);
     const uint16_t* xn = x + (int64_t)n * C * HW;
     uint32_t d[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    auto load_row = [&](int h) __attribute__((always_inline)) {
-        if (!sv) return;
-        const uint16_t* px = xn + (int64_t)h * W + sg;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint16_t* pj = px + j * HW;
-            d[j] = a.pair ? *reinterpret_cast<const uint32_t*>(pj) : ((uint32_t)pj[0] | ((uint32_t)pj[1] << 16));
-        }
-    };
-    auto write_row = [&](int pl) __attribute__((always_inline)) {
-        if (!sv) return;
-        unsigned char* pb = xpl + pl * PL;
-        *reinterpret_cast<uint4*>(pb + sl0) =
-            make_uint4(ppk_lo16(d[0], d[1]), ppk_lo16(d[2], d[3]), ppk_lo16(d[4], d[5]), ppk_lo16(d[6], d[7]));
-        *reinterpret_cast<uint4*>(pb + sl1) =
-            make_uint4(pk_hi16(d[0], d[1]), pk_hi16(d[2], d[3]), pk_hi16(d[4], d[5]), pk_hi16(d[6], d[7]));
-    };
+    auto load_row = [&](int h) __attribute__((always_inline)) { stage_load(st, xn + (int64_t)h * W, HW, a.pair, d); };
+    auto write_row = [&](int pl) __attribute__((always_inline)) { stage_write(st, xpl + pl * PL, d); };
 
     // ---- epilogue parameters.  conv 1 (transposed: a lane has the channels nt * 16 + 4 * o + i) reads its
     // 4 * NT triples from an LDS table [bias | scale | shift][C] when a mid row is finished; conv 2 (channel
@@ -275,47 +243,23 @@ __global__ __launch_bounds__(kPThreads) void conv_b16_pair(const uint16_t* __res
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 const int k = nt * 16 + (lane & 15);
-                const float rv[4] = {__uint_as_float(rres[g][nt][0] << 16), __uint_as_float(rres[g][nt][0] & 0xffff0000u),
-                                     __uint_as_float(rres[g][nt][1] << 16), __uint_as_float(rres[g][nt][1] & 0xffff0000u)};
-                uint32_t r[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float v = acc[g][0][nt][i] + eb[nt];
-                    if (aff) v = v * es[nt] + et[nt];
-                    if (a.add_x) v += rv[i];
-                    r[i] = bf16_rne(epi_act(v, act));  // the one rounding
-                }
                 *reinterpret_cast<uint2*>(tile + k * TP + (g * 16 + 4 * o) * 2) =
-                    make_uint2(r[0] | (r[1] << 16), r[2] | (r[3] << 16));
+                    finish4(acc[g][0][nt], eb[nt], aff, es[nt], et[nt], a.add_x, rres[g][nt][0], rres[g][nt][1], act);
             }
         }
-        // the tile is this wave's own: LDS executes a wave's accesses in order
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        tile_fence();
+        // the drain loop stays here: through tile_drain's for_pieces it measured 1.5 % slower on <16, 4> and 1 % on
+        // <32, 2> (profiles/bf16_rows_helpers_bisect.jsonl, arm "tile_drain")
 #pragma unroll
-        for (int it = 0; it < (C * CH + 63) / 64; ++it) {
+        for (int it = 0; it < pieces_per_lane(C, CH); ++it) {
             const int el = it * 64 + lane;
             const int k = el / CH, j = el % CH;
             const int qq = rw * (GW * 16) + j * 8;
             if (el >= C * CH || qq >= W) continue;  // (C = 16, GW = 1: 32 pieces;) idle groups, pieces past the row end
             const uint4 t4 = *reinterpret_cast<const uint4*>(tile + k * TP + j * 16);
-            uint16_t* yp = y + (((int64_t)n * C + k) * H + p) * W + qq;
-            const uint32_t t[4] = {t4.x, t4.y, t4.z, t4.w};
-            if (qq + 7 < W && (reinterpret_cast<uintptr_t>(yp) & 15u) == 0) {
-                *reinterpret_cast<uint4*>(yp) = t4;
-            } else if ((reinterpret_cast<uintptr_t>(yp) & 3u) == 0) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (qq + 2 * i < W) reinterpret_cast<uint32_t*>(yp)[i] = t[i];  // W, qq even: a whole pair
-            } else {
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    if (qq + i < W) yp[i] = (uint16_t)(t[i >> 1] >> (16 * (i & 1)));
-            }
+            store_piece(y + (((int64_t)n * C + k) * H + p) * W + qq, t4, qq, W);
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        tile_fence<false>();
     };
 
     // ---- prologue: the band's first x row (index 0 = image row p0 - 2; outside for the first band)
@@ -340,14 +284,7 @@ __global__ __launch_bounds__(kPThreads) void conv_b16_pair(const uint16_t* __res
             if (t >= 5) store_row(m - 1);
             if (a.add_x && m >= p0 && m < p0 + rbe) load_res((t - 2) & 3);  // y row m goes out in the next step
         }
-#pragma unroll
-        for (int g = 0; g < GW; ++g)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                acc[g][0][nt] = acc[g][1][nt];
-                acc[g][1][nt] = acc[g][2][nt];
-                acc[g][2][nt] = floatx4{0.f, 0.f, 0.f, 0.f};
-            }
+        rotate_acc(acc);
         __syncthreads();  // x plane (t + 1) & 3 and mid plane (t - 1) & 1 are written, the others read
     }
 }
@@ -359,8 +296,6 @@ hipError_t launch_pair_t(const B16PairPlan& p, const B16PArgs& a, const uint16_t
                        reinterpret_cast<const uint4*>(pk1), reinterpret_cast<const uint4*>(pk2), y, a);
     return hipGetLastError();
 }
-
-size_t pair_align256(size_t v) { return (v + 255) / 256 * 256; }
 
 }  // namespace
 
@@ -378,42 +313,23 @@ int b16_pair_plan(B16PairPlan& p, int64_t N, int64_t C, int64_t H, int64_t W) {
                   std::to_string(C) + ", got W = " + std::to_string(W));
         return 2;
     }
-    const int ngroups = (c.W + 15) / 16;
-    const int gpw = (ngroups + kPRole - 1) / kPRole;
-    const int GW = gpw <= 1 ? 1 : (gpw <= 2 ? 2 : 4);
-    // RB: conv_b16_rows' rule (16 rows, halved while the grid would leave CUs without a block)
-    int RB = 16;
-    while (RB > 4 && (int64_t)c.N * ((c.H + RB - 1) / RB) < 1024) RB >>= 1;
-    const int bands = (c.H + RB - 1) / RB;
-    const int64_t blocks = (int64_t)c.N * bands;
-    if (blocks > INT32_MAX) {
-        set_error("po2q: the bf16 conv pair: too many blocks");
-        return 2;
-    }
     c.taps = 9;
     c.vrx = 0; c.PS = 0; c.MI = 0; c.nts = 0; c.fp = 0; c.SB = 0; c.plane = 0;
     c.dma_d0 = c.dma_nck = c.dma_ni = c.dma_nw = c.dma_waves = c.dma_ov = 0;
-    c.kind = KIND_BF16_ROWS;
-    c.CC = c.C;
-    c.NT = c.C / 16;
-    c.NJ = GW;
-    c.TP = RB; c.TQ = c.W; c.tilesP = bands; c.tilesQ = ngroups;
-    c.kblocks = 1; c.nchunks = 1;
-    c.HH = RB + 4; c.WW = c.WWp = c.W + 2;
-    c.steps = pair_ks(c.C);
-    c.pd = kPXRing;
-    c.packed_floats = (int64_t)3 * c.steps * c.NT * 64 * 4;
-    p.GW = GW; p.RB = RB; p.bands = bands; p.ngroups = ngroups;
-    p.lds_bytes = (size_t)(kPXRing + kPMRing) * pair_plane(c.C, c.W) + (size_t)kPRole * c.C * pair_tpitch(GW) +
-                  (size_t)3 * c.C * sizeof(float);
-    p.blocks = blocks;
-    c.lds_bytes = p.lds_bytes;
-    c.blocks = blocks;
+    // 4 x planes + 2 mid planes, conv 1's epilogue table behind the tiles; a band reads 2 x rows either side
+    if (!fill_rows_plan(c, KIND_BF16_ROWS, kPXRing, kPXRing + kPMRing, 4, (size_t)3 * c.C * sizeof(float))) {
+        set_error("po2q: the bf16 conv pair: too many blocks");
+        return 2;
+    }
+    p.GW = c.NJ; p.RB = c.TP; p.bands = c.tilesP; p.ngroups = c.tilesQ;
+    p.lds_bytes = c.lds_bytes;
+    p.blocks = c.blocks;
     return 0;
 }
 
 // Workspace: [conv 1: max|w| partials, packed weight][conv 2: the same], each as b16_workspace_bytes lays it out
-size_t b16_pair_workspace_bytes(const B16PairPlan& p) { return 2 * pair_align256(b16_workspace_bytes(p.conv)); }
+// (a multiple of 256 bytes, so the second half is aligned as the first)
+size_t b16_pair_workspace_bytes(const B16PairPlan& p) { return 2 * b16_workspace_bytes(p.conv); }
 
 void b16_pair_describe(const B16PairPlan& p, char* buf, size_t len) {
     snprintf(buf, len, "kind=bf16_pair C=%d RB=%d bands=%d groups=%d GW=%d lds=%zu blocks=%lld", p.conv.C, p.RB, p.bands,
@@ -425,16 +341,16 @@ hipError_t b16_pair_run(const B16PairPlan& p, const uint16_t* x, const uint16_t*
                         const B16Epi& e2, int add_x, void* workspace, hipStream_t s) {
     // both weights through the batched pack: one max|w| launch (quantized modes) and one pack launch
     char* ws = reinterpret_cast<char*>(workspace);
-    const size_t half = pair_align256(b16_workspace_bytes(p.conv));
+    const size_t half = b16_workspace_bytes(p.conv);
     const B16PackReq reqs[2] = {{&p.conv, w1, ws, bits, fsr, mode}, {&p.conv, w2, ws + half, bits, fsr, mode}};
     const hipError_t pe = b16_pack_batch(2, reqs, s);
     if (pe != hipSuccess) return pe;
-    const size_t poff = pair_align256((size_t)256 * sizeof(uint32_t));  // b16_workspace_bytes' partials block
+    const size_t poff = b16_packed_offset();
     B16PArgs a;
     a.H = p.conv.H; a.W = p.conv.W;
     a.RB = p.RB; a.bands = p.bands; a.ngroups = p.ngroups;
-    a.plane = pair_plane(p.conv.C, p.conv.W);
-    a.pair = (reinterpret_cast<uintptr_t>(x) & 3u) == 0 ? 1 : 0;
+    a.plane = b16_rows_plane(p.conv.C, p.conv.W);
+    a.pair = b16_dword_aligned(x);
     a.add_x = add_x ? 1 : 0; a.act1 = e1.act; a.act2 = e2.act;
     a.b1 = bias1; a.b2 = bias2;
     a.ps1 = e1.ps; a.pb1 = e1.pb; a.ps2 = e2.ps; a.pb2 = e2.pb;

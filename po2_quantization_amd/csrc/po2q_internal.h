@@ -291,6 +291,7 @@ struct B16Epi {
 };
 int b16_plan(ConvPlan& p);
 size_t b16_workspace_bytes(const ConvPlan& p);
+size_t b16_packed_offset();  // of the packed weight inside that workspace, behind the max|w| partials
 void b16_describe(const ConvPlan& p, char* buf, size_t len);
 hipError_t b16_run(const ConvPlan& p, const uint16_t* x, const uint16_t* w, const uint16_t* bias, uint16_t* y,
                    int bits, int fsr, int mode, void* workspace, hipStream_t s, const B16Epi& e = B16Epi{});

@@ -37,6 +37,8 @@ typedef float floatx4 __attribute__((ext_vector_type(4)));
 // hi keeps +-inf, mid / lo are finite, and the products sum to +-inf as the reference's do.
 // (a >> 16) | (b & 0xffff0000): the bf16 halves of a (low) and b (high) as one dword
 __device__ __forceinline__ uint32_t pk_hi16(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
+// its partner, (a & 0xffff) | (b << 16): the low halves of a (low) and b (high) as one dword
+__device__ __forceinline__ uint32_t pk_lo16(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); }
 
 typedef float po2q_float2 __attribute__((ext_vector_type(2)));
 

@@ -4,6 +4,7 @@ the built library, no device.
 
 With the switch off nothing may differ from the library before the kernel existed: the descriptions and
 workspace sizes of tests/golden/bf16_rows_switch_off.json were written by that library."""
+import json
 import os
 import subprocess
 import sys
@@ -87,6 +88,36 @@ def test_switch_off_describes_and_sizes_as_before(shape, groups):
     assert desc.startswith("kind=dw_bf16 " if groups != 1 else "kind=bf16x1 ")
     assert rc.describe(shape, groups) == desc
     assert rc.workspace_bytes(shape, groups) == nbytes
+
+
+# ---- switches on: the plans of the three row-streaming kernels, byte for byte ---------------------------
+# tests/golden/bf16_rows_switch_on.json was written by the library before the three kernels' planners were
+# folded into fill_rows_plan: every shape of both row kernels' tables with both switches on, and every
+# eligible shape of the conv pair's table.
+def _load_switch_on():
+    with open(os.path.join(os.path.dirname(rc.GOLDEN), "bf16_rows_switch_on.json")) as f:
+        return [(e["entry"], tuple(e["shape"]), e["describe"], e["workspace_bytes"]) for e in json.load(f)]
+
+
+def test_switch_on_list_covers_every_table_shape():
+    from tests import _bf16_rowsk_cases as kc
+    from tests.test_bf16_pair_cpu import ELIGIBLE
+
+    listed = [(entry, shape) for entry, shape, _, _ in _load_switch_on()]
+    assert listed == [("conv", s) for s in rc.TABLE + kc.TABLE] + [("pair", s) for s in ELIGIBLE]
+
+
+@pytest.mark.parametrize("entry,shape,desc,nbytes", _load_switch_on(), ids=lambda v: cases.case_id(v) if isinstance(v, tuple) else None)
+def test_switches_on_describe_and_size_as_before(entry, shape, desc, nbytes):
+    if entry == "pair":
+        assert desc.startswith("kind=bf16_pair ")
+        assert _lib.describe_pair_bf16(*shape) == desc
+        assert _lib.load().po2q_qconv2d_pair_bf16_workspace_bytes(*shape, cases.BITS, 1, 1) == nbytes
+        return
+    assert desc.startswith("kind=bf16_rowsk " if shape[1] == 64 else "kind=bf16_rows ")
+    with _lib.bf16_rows(), _lib.bf16_rowsk():
+        assert rc.describe(shape) == desc
+        assert rc.workspace_bytes(shape) == nbytes
 
 
 def test_describe_shapes_of_the_existing_test_stay_on_the_tile_kernel():
