@@ -350,6 +350,21 @@ int po2q_qconv2d_pair_bf16_describe(int64_t N, int64_t C, int64_t H, int64_t W, 
                                     char* buf, size_t len);
 
 /*
+ * Fused multi-head self-attention core, fp32, forward only (reference models/mobile_vit.py:68-98, the lines of
+ * Attention.forward between to_qkv and to_out):
+ *   out[s, i, h*D + d] = sum_j softmax_j(scale * q_i . k_j) * v_j[d]        per sequence s and head h
+ * qkv [S, N, 3*H*D] contiguous, a token's row [q | k | v], each part H*D floats with head h at h*D .. h*D + D - 1
+ * (what to_qkv returns, viewed with S = batch * patch pixels); out [S, N, H*D] (what to_out consumes).  No
+ * chunk / transpose / reshape copy on either side, and no score or probability tensor in memory: one launch,
+ * a streaming softmax on fp32 MFMA (exact products, fp32 accumulation).  No mask, no dropout.
+ * Supported: heads == 4 and dim_head == 8 (the reference's Transformer(dim, depth, 4, 8, ...)), any S >= 1,
+ * any N >= 1; other heads / dim_head return PO2Q_ERR_INVALID -- there is no other path inside the library.
+ * N == 1 returns v bit for bit.  qkv and out must be 16-byte aligned and must not overlap.
+ * Asynchronous, no workspace, allocates nothing, safe under graph capture.
+ */
+int po2q_mhsa_f32(const float* qkv, float* out, int S, int N, int heads, int dim_head, float scale, void* stream);
+
+/*
  * Kernel autotuning, the counterpart of the reference's
  * torch.backends.cudnn.benchmark = True (train.py:33, test.py:31): times every
  * candidate plan for this problem on these buffers (synchronises the stream;

@@ -85,6 +85,7 @@ EXPORTS = (
     "po2q_qconv2d_pair_bf16_workspace_bytes",
     "po2q_qconv2d_pair_bf16",
     "po2q_qconv2d_pair_bf16_describe",
+    "po2q_mhsa_f32",
 )
 
 # Kernel autotuning on the first call per conv problem, the counterpart of
@@ -241,6 +242,8 @@ def load():
                                                                         p, sz, p])
     L.po2q_qconv2d_pair_bf16_describe.restype = i32
     L.po2q_qconv2d_pair_bf16_describe.argtypes = [i64] * 4 + [i32, i32, i32, ctypes.c_char_p, sz]
+    L.po2q_mhsa_f32.restype = i32
+    L.po2q_mhsa_f32.argtypes = [p, p, i32, i32, i32, i32, ctypes.c_float, p]
     _lib = L
     return L
 
@@ -632,6 +635,29 @@ def qconv2d_pair_bf16(x, w1, w2, bias1=None, bias2=None, bits=4, mode="po2", fsr
                                         ptr(ext2[0]), ptr(ext2[1]), 1 if add_x else 0, ACTS[act2], ws.data_ptr(),
                                         ws.numel(), _stream(xc.device)))
     return y
+
+
+def mhsa(qkv, heads, scale):
+    """The attention core of one layer in one launch (po2q_mhsa_f32): qkv [S, N, 3 * heads * 8] or
+    [b, p, N, 3 * heads * 8], fp32, contiguous, a token's row [q | k | v] with head h at h * 8 .. h * 8 + 7 of each
+    part (what Attention.to_qkv returns) -> softmax(scale * q k^T) v as [.., N, heads * 8] (what to_out consumes).
+    heads == 4 and dim_head == 8 only; anything else raises.  Forward only, no mask, no dropout."""
+    _require_hip_f32(qkv, "qkv")
+    if qkv.dim() not in (3, 4):
+        raise Po2qError("po2q: mhsa expects a 3-D or 4-D qkv, got %d-D" % qkv.dim())
+    O = ops()
+    if O is not None:
+        return _op_call(O.mhsa, qkv, int(heads), float(scale))
+    if not qkv.is_contiguous() or qkv.shape[-1] % (3 * int(heads)):
+        raise Po2qError("po2q: mhsa needs a contiguous qkv whose last dim is 3 * heads * dim_head")
+    out = torch.empty(qkv.shape[:-1] + (qkv.shape[-1] // 3,), dtype=torch.float32, device=qkv.device)
+    if out.numel() == 0:
+        return out
+    with torch.cuda.device(qkv.device):
+        _check(load().po2q_mhsa_f32(qkv.data_ptr(), out.data_ptr(), qkv.numel() // (qkv.shape[-1] * qkv.shape[-2]),
+                                    qkv.shape[-2], int(heads), qkv.shape[-1] // (3 * int(heads)), float(scale),
+                                    _stream(qkv.device)))
+    return out
 
 
 def set_bf16_row_kernels(on):

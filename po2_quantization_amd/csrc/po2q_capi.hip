@@ -823,6 +823,28 @@ int po2q_qconv2d_pair_bf16_describe(int64_t N, int64_t C, int64_t H, int64_t W, 
     return PO2Q_OK;
 }
 
+// ------------------------------------------------------------------ attention core --
+int po2q_mhsa_f32(const float* qkv, float* out, int S, int N, int heads, int dim_head, float scale, void* stream) {
+    if (!qkv || !out) {
+        set_error("po2q: null pointer");
+        return PO2Q_ERR_INVALID;
+    }
+    if (S <= 0 || N <= 0 || N > INT32_MAX - 16) {
+        set_error("po2q: mhsa needs positive S and N, got S = " + std::to_string(S) + ", N = " + std::to_string(N));
+        return PO2Q_ERR_INVALID;
+    }
+    if (!mhsa_supported(heads, dim_head)) {
+        set_error("po2q: mhsa takes heads == 4 and dim_head == 8, got heads = " + std::to_string(heads) +
+                  ", dim_head = " + std::to_string(dim_head));
+        return PO2Q_ERR_INVALID;
+    }
+    if ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(out)) & 15) {
+        set_error("po2q: mhsa needs 16-byte aligned qkv and out");
+        return PO2Q_ERR_INVALID;
+    }
+    return hip_status(launch_mhsa(qkv, out, S, N, scale, reinterpret_cast<hipStream_t>(stream)), "mhsa launch");
+}
+
 int po2q_bf16_set_row_kernels(int on) { return b16_rows_set(on); }
 
 int po2q_bf16_row_kernels(void) { return b16_rows_get(); }

@@ -356,6 +356,11 @@ hipError_t b16_pair_run(const B16PairPlan& p, const uint16_t* x, const uint16_t*
                         int bits, int fsr, int mode, const uint16_t* bias1, const uint16_t* bias2, const B16Epi& e1,
                         const B16Epi& e2, int add_x, void* workspace, hipStream_t s);
 
+// Fused fp32 multi-head self-attention core (po2q_mhsa.hip; po2q_mhsa_f32): qkv [S, N, 96] -> out [S, N, 32],
+// 4 heads of 8.  mhsa_supported: the (heads, dim_head) the kernels are written for.
+bool mhsa_supported(int heads, int dim_head);
+hipError_t launch_mhsa(const float* qkv, float* out, int S, int N, float scale, hipStream_t s);
+
 // lin / lin+ quantizer (po2q_lin.hip): w, out [d0, d1, rs = d2*d3], one block per d1 channel
 hipError_t launch_quantize_lin(const float* w, float* out, int d0, int d1, int rs, int bits, int num_iters, int plus,
                                hipStream_t s);

@@ -32,6 +32,8 @@
 //   po2q::qconv2d_pair_bf16  both convs of a bf16 identity BasicBlock in one launch (po2q_qconv2d_pair_bf16)
 //   po2q::qconv2d_pack_batch_bf16 / po2q::qconv2d_packed_bf16  the bf16 forward's weight staging of many
 //                        layers as batched launches, and each conv (+ epilogue) from its pack
+//   po2q::mhsa           the attention core of Attention.forward between to_qkv and to_out
+//                        (mobile_vit.py:68-98) in one launch (po2q_mhsa_f32); forward only
 // Meta kernels give the output shapes (FX / torch.compile tracing, fake tensors).
 // Errors are TORCH_CHECK -> RuntimeError, as F.conv2d raises for bad arguments.
 #include <ATen/ATen.h>
@@ -415,6 +417,44 @@ at::Tensor qconv2d_pair_bf16_meta(const at::Tensor& x, const at::Tensor&, const 
                                   const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&, bool, int64_t) {
     TORCH_CHECK(x.dim() == 4, "po2q: expected a 4-D input, got ", x.dim(), "-D");
     return at::empty(x.sizes(), x.options().dtype(at::kBFloat16));
+}
+
+// ---- fused attention core (po2q_mhsa_f32): qkv [.., N, 3 * heads * 8] -> [.., N, heads * 8] ----
+// 3-D [S, N, 3HD] or 4-D [b, p, N, 3HD] with the last three dims laid out contiguously and the sequences
+// evenly spaced (what nn.Linear returns); anything else raises -- no copy is made here
+std::vector<int64_t> mhsa_out_shape(const at::Tensor& qkv, int64_t heads) {
+    TORCH_CHECK(qkv.dim() == 3 || qkv.dim() == 4, "po2q: mhsa expects a 3-D or 4-D qkv, got ", qkv.dim(), "-D");
+    TORCH_CHECK(heads > 0 && qkv.size(-1) % (3 * heads) == 0, "po2q: mhsa: the last dim (", qkv.size(-1),
+                ") must be 3 * heads * dim_head with heads = ", heads);
+    std::vector<int64_t> shape(qkv.sizes().begin(), qkv.sizes().end());
+    shape.back() = qkv.size(-1) / 3;
+    return shape;
+}
+
+at::Tensor mhsa(const at::Tensor& qkv, int64_t heads, double scale) {
+    check_hip_f32(qkv, "qkv");
+    const std::vector<int64_t> shape = mhsa_out_shape(qkv, heads);
+    const int64_t N = qkv.size(-2), E = qkv.size(-1);
+    bool dense = true;  // size-1 dims may carry any stride
+    int64_t want = 1;
+    for (int64_t d = qkv.dim() - 1; d >= 0; --d) {
+        dense = dense && (qkv.size(d) == 1 || qkv.stride(d) == want);
+        want *= qkv.size(d);
+    }
+    TORCH_CHECK(dense, "po2q: mhsa needs a contiguous qkv (sizes ", qkv.sizes(), ", strides ", qkv.strides(), ")");
+    const int64_t S = qkv.dim() == 4 ? qkv.size(0) * qkv.size(1) : qkv.size(0);
+    TORCH_CHECK(S <= INT32_MAX && N <= INT32_MAX, "po2q: mhsa: S = ", S, " / N = ", N, " out of range");
+    const DeviceGuard guard(qkv.device());
+    at::Tensor out = at::empty(shape, qkv.options());
+    if (out.numel() == 0) return out;
+    const int st = po2q_mhsa_f32(qkv.data_ptr<float>(), out.data_ptr<float>(), (int)S, (int)N, (int)heads,
+                                 (int)(E / (3 * heads)), (float)scale, stream_of(qkv));
+    TORCH_CHECK(st == 0, last_error());
+    return out;
+}
+
+at::Tensor mhsa_meta(const at::Tensor& qkv, int64_t heads, double) {
+    return at::empty(mhsa_out_shape(qkv, heads), qkv.options());
 }
 
 // ---- batched weight staging of the bf16 forward (po2q_qconv2d_bf16_pack_batch / _packed_bf16) ----
@@ -1127,6 +1167,7 @@ TORCH_LIBRARY(po2q, m) {
     m.def("qconv2d_pair_bf16(Tensor x, Tensor w1, Tensor w2, Tensor? bias1, Tensor? bias2, int bits, int mode, "
           "int fsr=1, Tensor? post_scale1=None, Tensor? post_shift1=None, int act1=0, Tensor? post_scale2=None, "
           "Tensor? post_shift2=None, bool add_x=False, int act2=0) -> Tensor");
+    m.def("mhsa(Tensor qkv, int heads, float scale) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(po2q, CUDA, m) {  // the HIP device (PyTorch-ROCm dispatches HIP tensors under CUDA)
@@ -1147,6 +1188,7 @@ TORCH_LIBRARY_IMPL(po2q, CUDA, m) {  // the HIP device (PyTorch-ROCm dispatches 
     m.impl("qconv2d_pack_batch_bf16", &qconv2d_pack_batch_bf16);
     m.impl("qconv2d_packed_bf16", &qconv2d_packed_bf16);
     m.impl("qconv2d_pair_bf16", &qconv2d_pair_bf16);
+    m.impl("mhsa", &mhsa);
 }
 
 TORCH_LIBRARY_IMPL(po2q, Meta, m) {
@@ -1167,4 +1209,5 @@ TORCH_LIBRARY_IMPL(po2q, Meta, m) {
     m.impl("qconv2d_pack_batch_bf16", &qconv2d_pack_batch_bf16_meta);
     m.impl("qconv2d_packed_bf16", &qconv2d_packed_bf16_meta);
     m.impl("qconv2d_pair_bf16", &qconv2d_pair_bf16_meta);
+    m.impl("mhsa", &mhsa_meta);
 }

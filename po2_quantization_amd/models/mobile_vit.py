@@ -14,20 +14,29 @@ The module tree reproduces the reference's nesting, so state_dict keys match:
 
 Only the QuantizedConv2d layers are quantized (the reference quantizes no
 Linear / attention weight, :56-128); attention, LayerNorm and the MLP stay
-plain torch ops -- they are off the graded path.  nxn convs use padding 1 as
+plain torch ops -- they are off the graded path -- except that NATIVE_ATTENTION
+(below) runs the attention core as one fused launch.  nxn convs use padding 1 as
 in the reference (:32), whatever kernel_size is.  einops' rearranges are
 spelled as view/permute (same element order).
 
 Note: at 224x224 the reference raises (7x7 map, 2x2 patches, :282 -- SURVEY
 §7); this mirror raises the same way (a RuntimeError from the reshape).
 """
+import os
 from typing import Any, Callable, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
+from .. import _lib
 from .quantized_conv import (QuantizedConv2d, batched_packs, can_fuse, fusable_sequence, run_fused_sequence,
                              run_inverted_residual, run_sequence)
+
+
+# Opt-in: eval / no-grad fp32 HIP forwards run the attention core (everything between to_qkv and to_out) as one
+# fused launch, _lib.mhsa (po2q_mhsa_f32), instead of the torch op sequence.  PO2Q_NATIVE_ATTENTION=1 sets it
+# at import; ptq.py --native-attention and tools/model_bench.py --native-attention set it for a run.
+NATIVE_ATTENTION = os.environ.get("PO2Q_NATIVE_ATTENTION") == "1"
 
 
 def quantized_conv_1x1_bn(inp, oup, quantize_fn=None, bits=4):
@@ -74,8 +83,13 @@ class Attention(nn.Module):
 
     def forward(self, x):
         b, p, n, _ = x.shape
+        qkv = self.to_qkv(self.norm(x))
+        if (NATIVE_ATTENTION and qkv.device.type == "cuda" and qkv.dtype == torch.float32 and not qkv.requires_grad
+                and not (self.training and self.dropout.p > 0)):
+            # fp32 HIP forward with no gradient recorded and no active dropout: one fused launch, no copies
+            return self.to_out(_lib.mhsa(qkv, self.heads, self.scale))
         # [b, p, n, 3*h*d] -> q, k, v each [b, p, h, n, d]
-        q, k, v = (t.view(b, p, n, self.heads, -1).transpose(2, 3) for t in self.to_qkv(self.norm(x)).chunk(3, dim=-1))
+        q, k, v = (t.view(b, p, n, self.heads, -1).transpose(2, 3) for t in qkv.chunk(3, dim=-1))
         attn = self.dropout(self.attend(torch.matmul(q, k.transpose(-1, -2)) * self.scale))
         out = torch.matmul(attn, v).transpose(2, 3).reshape(b, p, n, -1)
         return self.to_out(out)

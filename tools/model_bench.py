@@ -14,7 +14,13 @@ The bf16 forward (model.bfloat16(), bf16 input) in four arms: both row-kernel sw
 both on, both on with the fused epilogue (models.quantized_conv.BF16_FUSED_EPILOGUE).  The arms named by
 the flags are timed (no flag: all four), alternated forward by forward in one process with HIP events
 around each whole forward; one JSON line with every run's median milliseconds per arm and the spread
-between runs."""
+between runs.
+
+    python tools/model_bench.py --model mobilevit --image 256 --batch 64 --graph --only-fused --native-attention [--runs 3]
+
+The fp32 fused forward of MobileViT with the torch attention core against the fused one (models.mobile_vit.
+NATIVE_ATTENTION, po2q_mhsa_f32): both arms in one process, as captured graphs with --graph, timed in alternating runs;
+every run's milliseconds per arm, the spread within an arm and the logits' normwise difference join the JSON line."""
 import argparse
 import json
 import os
@@ -27,7 +33,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from po2_quantization_amd import _lib  # noqa: E402
-from po2_quantization_amd.models import quantized_conv  # noqa: E402
+from po2_quantization_amd.models import mobile_vit, quantized_conv  # noqa: E402
 from po2_quantization_amd.models.model import get_model  # noqa: E402
 from po2_quantization_amd.utils.quantizers import quantizer_dict  # noqa: E402
 
@@ -131,7 +137,11 @@ def main():
     ap.add_argument("--bf16-fused-epilogue", action="store_true", help="with --dtype bf16: ... with the fused epilogue")
     ap.add_argument("--bf16-pairs", action="store_true",
                     help="with --dtype bf16 --bf16-fused-epilogue: ... with the identity blocks as conv pairs")
-    ap.add_argument("--runs", type=int, default=2, help="with --dtype bf16: timed runs (the spread is between their medians)")
+    ap.add_argument("--runs", type=int, default=2, help="with --dtype bf16 or --native-attention: timed runs per arm (the spread is between them)")
+    ap.add_argument("--native-attention", action="store_true",
+                    help="fp32 mobilevit: also time the fused forward with the attention core as one fused launch "
+                         "(models.mobile_vit.NATIVE_ATTENTION) beside the torch attention, eager or with --graph "
+                         "replayed from a graph each, the two arms alternating over --runs timed runs")
     args = ap.parse_args()
     if args.dtype == "bf16":
         return bench_bf16(args)
@@ -155,8 +165,7 @@ def main():
             t = timed(lambda: m(x), args.steps, args.warmup)
             res[name + "_ms"] = round(t * 1e3, 3)
             res[name + "_images_per_s"] = round(args.batch / t, 1)
-        if args.graph:
-            quantized_conv.INFERENCE_FUSION = True
+        def capture():
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
@@ -165,9 +174,38 @@ def main():
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 m(x)
+            return g
+
+        if args.graph:
+            quantized_conv.INFERENCE_FUSION = True
+            g = capture()
             t = timed(g.replay, args.steps * 4, args.warmup)
             res["graph_fused_ms"] = round(t * 1e3, 3)
             res["graph_fused_images_per_s"] = round(args.batch / t, 1)
+        if args.native_attention:
+            # the same fused forward, torch attention against the fused attention core, in alternating timed runs
+            quantized_conv.INFERENCE_FUSION = True
+            saved = mobile_vit.NATIVE_ATTENTION
+            try:
+                fns = {}
+                for name, on in (("torch_attention", False), ("native_attention", True)):
+                    mobile_vit.NATIVE_ATTENTION = on
+                    res[name + "_logits"] = m(x)
+                    fns[name] = capture().replay if args.graph else (lambda on=on: m(x))
+                runs = {name: [] for name in fns}
+                for _ in range(args.runs):
+                    for name, fn in fns.items():
+                        mobile_vit.NATIVE_ATTENTION = name == "native_attention"
+                        runs[name].append(timed(fn, args.steps * (4 if args.graph else 1), args.warmup) * 1e3)
+            finally:
+                mobile_vit.NATIVE_ATTENTION = saved
+            ref, got = res.pop("torch_attention_logits"), res.pop("native_attention_logits")
+            res["native_attention_vs_torch_normwise"] = float((got - ref).abs().max() / ref.abs().max())
+            res["attention_arms_graph"] = bool(args.graph)
+            for name, v in runs.items():
+                res[name + "_runs_ms"] = [round(t, 3) for t in v]
+                res[name + "_images_per_s"] = round(args.batch / (statistics.median(v) * 1e-3), 1)
+            res["spread_ms"] = round(max(max(v) - min(v) for v in runs.values()), 3)
         if not args.only_fused:
             quantized_conv.INFERENCE_FUSION = True
             ya = m(x)
