@@ -365,6 +365,28 @@ int po2q_qconv2d_pair_bf16_describe(int64_t N, int64_t C, int64_t H, int64_t W, 
 int po2q_mhsa_f32(const float* qkv, float* out, int S, int N, int heads, int dim_head, float scale, void* stream);
 
 /*
+ * Fused transformer MLP, fp32, forward only (reference models/mobile_vit.py:56-65 FeedForward and the add of
+ * Transformer.forward :108-109, dropout 0):
+ *   out[m, :] = x[m, :] + W2 . SiLU(W1 . LN(x[m, :]) + b1) + b2          per token m (the "x +" if residual != 0)
+ * LN = LayerNorm over dim with weight ln_w, bias ln_b and eps.  x, out [M, dim] contiguous; ln_w, ln_b, b2 [dim];
+ * w1 [hidden, dim] and w2 [dim, hidden] row-major as nn.Linear.weight stores them (nothing is transposed or packed
+ * on the host); b1 [hidden].  One launch on fp32 MFMA (exact products, fp32 accumulation); the [M, hidden]
+ * activations never reach memory.
+ * kernel: PO2Q_FFN_AUTO picks by M alone; PO2Q_FFN_TOKEN_TILES (many tokens: a block runs 128 tokens against
+ * weights staged through LDS) and PO2Q_FFN_HIDDEN_SPLIT (few tokens: a block is 16 tokens, its waves split the
+ * hidden dimension) force one; both take every supported shape.
+ * Supported: M >= 1; dim % 4 == 0 and 4 <= dim <= PO2Q_FFN_MAX_DIM (the largest multiple of 16 at which both
+ * kernels compile without scratch memory); hidden % 4 == 0 and hidden >= 4; every pointer non-NULL and 16-byte
+ * aligned; out must not overlap x.  Anything else returns PO2Q_ERR_INVALID before any launch -- there is no other
+ * path inside the library.  Asynchronous, no workspace, allocates nothing, safe under graph capture.
+ */
+enum po2q_ffn_kernel { PO2Q_FFN_AUTO = 0, PO2Q_FFN_TOKEN_TILES = 1, PO2Q_FFN_HIDDEN_SPLIT = 2 };
+#define PO2Q_FFN_MAX_DIM 464
+int po2q_ffn_f32(const float* x, const float* ln_w, const float* ln_b, float eps,
+                 const float* w1, const float* b1, const float* w2, const float* b2,
+                 float* out, int M, int dim, int hidden, int residual, int kernel, void* stream);
+
+/*
  * Kernel autotuning, the counterpart of the reference's
  * torch.backends.cudnn.benchmark = True (train.py:33, test.py:31): times every
  * candidate plan for this problem on these buffers (synchronises the stream;

@@ -86,6 +86,7 @@ EXPORTS = (
     "po2q_qconv2d_pair_bf16",
     "po2q_qconv2d_pair_bf16_describe",
     "po2q_mhsa_f32",
+    "po2q_ffn_f32",
 )
 
 # Kernel autotuning on the first call per conv problem, the counterpart of
@@ -244,6 +245,8 @@ def load():
     L.po2q_qconv2d_pair_bf16_describe.argtypes = [i64] * 4 + [i32, i32, i32, ctypes.c_char_p, sz]
     L.po2q_mhsa_f32.restype = i32
     L.po2q_mhsa_f32.argtypes = [p, p, i32, i32, i32, i32, ctypes.c_float, p]
+    L.po2q_ffn_f32.restype = i32
+    L.po2q_ffn_f32.argtypes = [p, p, p, ctypes.c_float, p, p, p, p, p, i32, i32, i32, i32, i32, p]
     _lib = L
     return L
 
@@ -657,6 +660,35 @@ def mhsa(qkv, heads, scale):
         _check(load().po2q_mhsa_f32(qkv.data_ptr(), out.data_ptr(), qkv.numel() // (qkv.shape[-1] * qkv.shape[-2]),
                                     qkv.shape[-2], int(heads), qkv.shape[-1] // (3 * int(heads)), float(scale),
                                     _stream(qkv.device)))
+    return out
+
+
+def ffn(x, ln_w, ln_b, eps, w1, b1, w2, b2, residual=True, kernel=0):
+    """x + FeedForward(x) of a transformer layer in one launch (po2q_ffn_f32):
+    x + W2 SiLU(W1 LayerNorm(x) + b1) + b2 per token (without the "x +" if residual is False).  x [.., dim] of rank
+    >= 2, fp32, contiguous; ln_w, ln_b [dim], w1 [hidden, dim], b1 [hidden], w2 [dim, hidden], b2 [dim] as
+    nn.LayerNorm / nn.Linear store them.  kernel: 0 picks by the token count, 1 forces the token-tile kernel, 2 the
+    hidden-split kernel.  dim and hidden are multiples of 4, dim <= 464; anything else raises.  Forward only."""
+    for t, name in ((x, "x"), (ln_w, "ln_w"), (ln_b, "ln_b"), (w1, "w1"), (b1, "b1"), (w2, "w2"), (b2, "b2")):
+        _require_hip_f32(t, name)
+    if x.dim() < 2:
+        raise Po2qError("po2q: ffn expects x of rank >= 2, got %d-D" % x.dim())
+    O = ops()
+    if O is not None:
+        return _op_call(O.ffn, x, ln_w, ln_b, float(eps), w1, b1, w2, b2, bool(residual), int(kernel))
+    dim, hidden = x.shape[-1], w1.shape[0]
+    if (not all(t.is_contiguous() for t in (x, ln_w, ln_b, w1, b1, w2, b2)) or tuple(w1.shape) != (hidden, dim)
+            or tuple(w2.shape) != (dim, hidden) or not ln_w.numel() == ln_b.numel() == b2.numel() == dim
+            or b1.numel() != hidden):
+        raise Po2qError("po2q: ffn needs contiguous tensors: x [.., dim], ln_w / ln_b / b2 [dim], w1 [hidden, dim], "
+                        "b1 [hidden], w2 [dim, hidden]")
+    out = torch.empty_like(x)
+    if out.numel() == 0:
+        return out
+    with torch.cuda.device(x.device):
+        _check(load().po2q_ffn_f32(x.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), float(eps), w1.data_ptr(),
+                                   b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), out.data_ptr(), x.numel() // dim, dim,
+                                   hidden, int(bool(residual)), int(kernel), _stream(x.device)))
     return out
 
 

@@ -845,6 +845,50 @@ int po2q_mhsa_f32(const float* qkv, float* out, int S, int N, int heads, int dim
     return hip_status(launch_mhsa(qkv, out, S, N, scale, reinterpret_cast<hipStream_t>(stream)), "mhsa launch");
 }
 
+// ------------------------------------------------------------ transformer MLP --
+int po2q_ffn_f32(const float* x, const float* ln_w, const float* ln_b, float eps, const float* w1, const float* b1,
+                 const float* w2, const float* b2, float* out, int M, int dim, int hidden, int residual, int kernel,
+                 void* stream) {
+    const void* ptrs[] = {x, ln_w, ln_b, w1, b1, w2, b2, out};
+    uintptr_t bits = 0;
+    for (const void* q : ptrs) {
+        if (!q) {
+            set_error("po2q: null pointer");
+            return PO2Q_ERR_INVALID;
+        }
+        bits |= reinterpret_cast<uintptr_t>(q);
+    }
+    if (M <= 0) {
+        set_error("po2q: ffn needs a positive M, got M = " + std::to_string(M));
+        return PO2Q_ERR_INVALID;
+    }
+    if (dim < 4 || dim % 4 || dim > PO2Q_FFN_MAX_DIM) {
+        set_error("po2q: ffn takes dim % 4 == 0 with 4 <= dim <= " + std::to_string(PO2Q_FFN_MAX_DIM) +
+                  ", got dim = " + std::to_string(dim));
+        return PO2Q_ERR_INVALID;
+    }
+    if (hidden < 4 || hidden % 4) {
+        set_error("po2q: ffn takes hidden % 4 == 0 with hidden >= 4, got hidden = " + std::to_string(hidden));
+        return PO2Q_ERR_INVALID;
+    }
+    if (kernel != PO2Q_FFN_AUTO && kernel != PO2Q_FFN_TOKEN_TILES && kernel != PO2Q_FFN_HIDDEN_SPLIT) {
+        set_error("po2q: ffn: unknown kernel " + std::to_string(kernel) + " (0 auto, 1 token tiles, 2 hidden split)");
+        return PO2Q_ERR_INVALID;
+    }
+    if (bits & 15) {
+        set_error("po2q: ffn needs 16-byte aligned pointers");
+        return PO2Q_ERR_INVALID;
+    }
+    const uintptr_t xb = reinterpret_cast<uintptr_t>(x), ob = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t bytes = (uintptr_t)M * dim * sizeof(float);
+    if (xb < ob + bytes && ob < xb + bytes) {
+        set_error("po2q: ffn: out must not overlap x");
+        return PO2Q_ERR_INVALID;
+    }
+    const FfnArgs a{x, ln_w, ln_b, w1, b1, w2, b2, out, M, dim, hidden, residual != 0, eps};
+    return hip_status(launch_ffn(a, kernel, reinterpret_cast<hipStream_t>(stream)), "ffn launch");
+}
+
 int po2q_bf16_set_row_kernels(int on) { return b16_rows_set(on); }
 
 int po2q_bf16_row_kernels(void) { return b16_rows_get(); }

@@ -361,6 +361,16 @@ hipError_t b16_pair_run(const B16PairPlan& p, const uint16_t* x, const uint16_t*
 bool mhsa_supported(int heads, int dim_head);
 hipError_t launch_mhsa(const float* qkv, float* out, int S, int N, float scale, hipStream_t s);
 
+// Fused LayerNorm + MLP + residual (po2q_ffn.hip; po2q_ffn_f32): out = x + W2 SiLU(W1 LN(x) + b1) + b2 per token.
+// kernel: a po2q_ffn_kernel value; the C entry has checked every argument (dim <= PO2Q_FFN_MAX_DIM included).
+struct FfnArgs {
+    const float *x, *ln_w, *ln_b, *w1, *b1, *w2, *b2;
+    float* out;
+    int M, dim, hidden, residual;
+    float eps;
+};
+hipError_t launch_ffn(const FfnArgs& a, int kernel, hipStream_t s);
+
 // lin / lin+ quantizer (po2q_lin.hip): w, out [d0, d1, rs = d2*d3], one block per d1 channel
 hipError_t launch_quantize_lin(const float* w, float* out, int d0, int d1, int rs, int bits, int num_iters, int plus,
                                hipStream_t s);

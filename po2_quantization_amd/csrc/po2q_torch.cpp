@@ -34,6 +34,8 @@
 //                        layers as batched launches, and each conv (+ epilogue) from its pack
 //   po2q::mhsa           the attention core of Attention.forward between to_qkv and to_out
 //                        (mobile_vit.py:68-98) in one launch (po2q_mhsa_f32); forward only
+//   po2q::ffn            x + FeedForward(x) of a transformer layer (LayerNorm, Linear, SiLU, Linear, add) in one
+//                        launch (po2q_ffn_f32); forward only
 // Meta kernels give the output shapes (FX / torch.compile tracing, fake tensors).
 // Errors are TORCH_CHECK -> RuntimeError, as F.conv2d raises for bad arguments.
 #include <ATen/ATen.h>
@@ -455,6 +457,49 @@ at::Tensor mhsa(const at::Tensor& qkv, int64_t heads, double scale) {
 
 at::Tensor mhsa_meta(const at::Tensor& qkv, int64_t heads, double) {
     return at::empty(mhsa_out_shape(qkv, heads), qkv.options());
+}
+
+// ---- fused transformer MLP (po2q_ffn_f32): x [.., dim] -> [.., dim] ----
+// x of any rank >= 2, contiguous; the parameters as nn.LayerNorm / nn.Linear store them; no copy is made here
+void ffn_check_x(const at::Tensor& x) {
+    TORCH_CHECK(x.dim() >= 2, "po2q: ffn expects x of rank >= 2, got ", x.dim(), "-D");
+}
+
+at::Tensor ffn(const at::Tensor& x, const at::Tensor& ln_w, const at::Tensor& ln_b, double eps, const at::Tensor& w1,
+               const at::Tensor& b1, const at::Tensor& w2, const at::Tensor& b2, bool residual, int64_t kernel) {
+    ffn_check_x(x);
+    const at::Tensor* all[] = {&x, &ln_w, &ln_b, &w1, &b1, &w2, &b2};
+    const char* names[] = {"x", "ln_w", "ln_b", "w1", "b1", "w2", "b2"};
+    for (int i = 0; i < 7; ++i) {
+        check_hip_f32(*all[i], names[i]);
+        TORCH_CHECK(all[i]->is_contiguous(), "po2q: ffn needs a contiguous ", names[i]);
+        TORCH_CHECK(all[i]->device() == x.device(), "po2q: ffn: ", names[i], " is on another device than x");
+    }
+    const int64_t dim = x.size(-1);
+    TORCH_CHECK(w1.dim() == 2 && w1.size(1) == dim, "po2q: ffn: w1 must be [hidden, ", dim, "], got ", w1.sizes());
+    const int64_t hidden = w1.size(0);
+    TORCH_CHECK(w2.dim() == 2 && w2.size(0) == dim && w2.size(1) == hidden, "po2q: ffn: w2 must be [", dim, ", ",
+                hidden, "], got ", w2.sizes());
+    TORCH_CHECK(ln_w.numel() == dim && ln_b.numel() == dim && b2.numel() == dim && b1.numel() == hidden,
+                "po2q: ffn: ln_w, ln_b, b2 must hold dim = ", dim, " and b1 hidden = ", hidden, " values");
+    const int64_t M = dim ? x.numel() / dim : 0;
+    TORCH_CHECK(M <= INT32_MAX && dim <= INT32_MAX && hidden <= INT32_MAX, "po2q: ffn: M = ", M, " / dim = ", dim,
+                " / hidden = ", hidden, " out of range");
+    const DeviceGuard guard(x.device());
+    at::Tensor out = at::empty(x.sizes(), x.options());
+    if (out.numel() == 0) return out;
+    const int st = po2q_ffn_f32(x.data_ptr<float>(), ln_w.data_ptr<float>(), ln_b.data_ptr<float>(), (float)eps,
+                                w1.data_ptr<float>(), b1.data_ptr<float>(), w2.data_ptr<float>(), b2.data_ptr<float>(),
+                                out.data_ptr<float>(), (int)M, (int)dim, (int)hidden, residual ? 1 : 0, (int)kernel,
+                                stream_of(x));
+    TORCH_CHECK(st == 0, last_error());
+    return out;
+}
+
+at::Tensor ffn_meta(const at::Tensor& x, const at::Tensor&, const at::Tensor&, double, const at::Tensor&,
+                    const at::Tensor&, const at::Tensor&, const at::Tensor&, bool, int64_t) {
+    ffn_check_x(x);
+    return at::empty(x.sizes(), x.options());
 }
 
 // ---- batched weight staging of the bf16 forward (po2q_qconv2d_bf16_pack_batch / _packed_bf16) ----
@@ -1168,6 +1213,8 @@ TORCH_LIBRARY(po2q, m) {
           "int fsr=1, Tensor? post_scale1=None, Tensor? post_shift1=None, int act1=0, Tensor? post_scale2=None, "
           "Tensor? post_shift2=None, bool add_x=False, int act2=0) -> Tensor");
     m.def("mhsa(Tensor qkv, int heads, float scale) -> Tensor");
+    m.def("ffn(Tensor x, Tensor ln_w, Tensor ln_b, float eps, Tensor w1, Tensor b1, Tensor w2, Tensor b2, "
+          "bool residual, int kernel) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(po2q, CUDA, m) {  // the HIP device (PyTorch-ROCm dispatches HIP tensors under CUDA)
@@ -1189,6 +1236,7 @@ TORCH_LIBRARY_IMPL(po2q, CUDA, m) {  // the HIP device (PyTorch-ROCm dispatches 
     m.impl("qconv2d_packed_bf16", &qconv2d_packed_bf16);
     m.impl("qconv2d_pair_bf16", &qconv2d_pair_bf16);
     m.impl("mhsa", &mhsa);
+    m.impl("ffn", &ffn);
 }
 
 TORCH_LIBRARY_IMPL(po2q, Meta, m) {
@@ -1210,4 +1258,5 @@ TORCH_LIBRARY_IMPL(po2q, Meta, m) {
     m.impl("qconv2d_packed_bf16", &qconv2d_packed_bf16_meta);
     m.impl("qconv2d_pair_bf16", &qconv2d_pair_bf16_meta);
     m.impl("mhsa", &mhsa_meta);
+    m.impl("ffn", &ffn_meta);
 }

@@ -15,7 +15,8 @@ The module tree reproduces the reference's nesting, so state_dict keys match:
 Only the QuantizedConv2d layers are quantized (the reference quantizes no
 Linear / attention weight, :56-128); attention, LayerNorm and the MLP stay
 plain torch ops -- they are off the graded path -- except that NATIVE_ATTENTION
-(below) runs the attention core as one fused launch.  nxn convs use padding 1 as
+(below) runs the attention core as one fused launch, and NATIVE_FFN each
+layer's x + FeedForward(x) as another.  nxn convs use padding 1 as
 in the reference (:32), whatever kernel_size is.  einops' rearranges are
 spelled as view/permute (same element order).
 
@@ -37,6 +38,11 @@ from .quantized_conv import (QuantizedConv2d, batched_packs, can_fuse, fusable_s
 # fused launch, _lib.mhsa (po2q_mhsa_f32), instead of the torch op sequence.  PO2Q_NATIVE_ATTENTION=1 sets it
 # at import; ptq.py --native-attention and tools/model_bench.py --native-attention set it for a run.
 NATIVE_ATTENTION = os.environ.get("PO2Q_NATIVE_ATTENTION") == "1"
+
+# Opt-in, independent of the above: the same forwards run x + FeedForward(x) of every transformer layer (LayerNorm,
+# Linear, SiLU, Linear and the add) as one fused launch, _lib.ffn (po2q_ffn_f32).  PO2Q_NATIVE_FFN=1 sets it at
+# import; ptq.py --native-ffn and tools/model_bench.py --native-ffn set it for a run.
+NATIVE_FFN = os.environ.get("PO2Q_NATIVE_FFN") == "1"
 
 
 def quantized_conv_1x1_bn(inp, oup, quantize_fn=None, bits=4):
@@ -105,6 +111,15 @@ class Transformer(nn.Module):
     def forward(self, x):
         for attn, ff in self.layers:
             x = x + attn(x)
+            if (NATIVE_FFN and x.device.type == "cuda" and x.dtype == torch.float32 and not x.requires_grad
+                    and not (ff.training and ff.net[3].p > 0)):
+                # fp32 HIP forward with no gradient recorded and no active dropout: one fused launch
+                norm, fc1, fc2 = ff.net[0], ff.net[1], ff.net[4]
+                # (1x1 patches make MobileViTBlock's rearrange a strided view and the add above keeps its layout:
+                # the kernel reads rows, so the first layer copies once; its output is contiguous for the others)
+                x = _lib.ffn(x.contiguous(), norm.weight, norm.bias, norm.eps, fc1.weight, fc1.bias, fc2.weight,
+                             fc2.bias)
+                continue
             x = x + ff(x)
         return x
 

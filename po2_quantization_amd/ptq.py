@@ -150,7 +150,8 @@ def tensor_loader(data_file: str, batch_size: int):
 def main(model_type: str, dataset: str, data_file: str, batch_size: int = 128, train_dir: str = "./train",
          results_dir: str = "./results", skip_qat: bool = False, dtype: str = "fp32",
          bf16_fused_epilogue: bool = False, bf16_row_kernels: bool = False,
-         bf16_rowsk_kernels: bool = False, bf16_pairs: bool = False, native_attention: bool = False) -> None:
+         bf16_rowsk_kernels: bool = False, bf16_pairs: bool = False, native_attention: bool = False,
+         native_ffn: bool = False) -> None:
     """test.py:58-164 with the evaluation set from data_file."""
     assert dtype in DTYPES, "invalid dtype"
     assert not bf16_fused_epilogue or dtype == "bf16", "--bf16-fused-epilogue needs --dtype bf16"
@@ -175,6 +176,8 @@ def main(model_type: str, dataset: str, data_file: str, batch_size: int = 128, t
     quantized_conv.BF16_PAIRS = bool(bf16_pairs)  # for this run
     saved_attention = mobile_vit.NATIVE_ATTENTION
     mobile_vit.NATIVE_ATTENTION = bool(native_attention) or saved_attention  # for this run
+    saved_ffn = mobile_vit.NATIVE_FFN
+    mobile_vit.NATIVE_FFN = bool(native_ffn) or saved_ffn  # for this run
     saved_rows = _lib.set_bf16_row_kernels(bool(bf16_row_kernels))  # for this run
     saved_rowsk = _lib.set_bf16_rowsk_kernels(bool(bf16_rowsk_kernels))  # for this run
     try:
@@ -187,6 +190,7 @@ def main(model_type: str, dataset: str, data_file: str, batch_size: int = 128, t
         quantized_conv.BF16_FUSED_EPILOGUE = saved
         quantized_conv.BF16_PAIRS = saved_pairs
         mobile_vit.NATIVE_ATTENTION = saved_attention
+        mobile_vit.NATIVE_FFN = saved_ffn
         _lib.set_bf16_row_kernels(saved_rows)
         _lib.set_bf16_rowsk_kernels(saved_rowsk)
 
@@ -213,6 +217,9 @@ def arg_parser():
     ap.add_argument("--native-attention", action="store_true",
                     help="mobilevit in fp32: the attention core of every transformer layer as one fused launch "
                          "(models.mobile_vit.NATIVE_ATTENTION), for this run")
+    ap.add_argument("--native-ffn", action="store_true",
+                    help="mobilevit in fp32: LayerNorm + MLP + residual of every transformer layer as one fused launch "
+                         "(models.mobile_vit.NATIVE_FFN), for this run")
     ap.add_argument("--bf16-row-kernels", action="store_true",
                     help="with --dtype bf16: the row-streaming conv kernel for the 3x3 stride-1 C = K = 16 / 32 "
                          "layers (_lib.set_bf16_row_kernels), for this run")
@@ -225,4 +232,5 @@ def arg_parser():
 if __name__ == "__main__":
     a = arg_parser().parse_args()
     main(a.model_type, a.dataset, a.data_file, a.batch_size, a.train_dir, a.results_dir, a.skip_qat, a.dtype,
-         a.bf16_fused_epilogue, a.bf16_row_kernels, a.bf16_rowsk_kernels, a.bf16_pairs, a.native_attention)
+         a.bf16_fused_epilogue, a.bf16_row_kernels, a.bf16_rowsk_kernels, a.bf16_pairs, a.native_attention,
+         a.native_ffn)

@@ -20,7 +20,9 @@ between runs.
 
 The fp32 fused forward of MobileViT with the torch attention core against the fused one (models.mobile_vit.
 NATIVE_ATTENTION, po2q_mhsa_f32): both arms in one process, as captured graphs with --graph, timed in alternating runs;
-every run's milliseconds per arm, the spread within an arm and the logits' normwise difference join the JSON line."""
+every run's milliseconds per arm, the spread within an arm and the logits' normwise difference join the JSON line.
+--native-ffn adds an arm with the fused LayerNorm + MLP + residual launch (models.mobile_vit.NATIVE_FFN, po2q_ffn_f32):
+on top of the fused attention when --native-attention is given too, on the torch attention otherwise."""
 import argparse
 import json
 import os
@@ -142,6 +144,10 @@ def main():
                     help="fp32 mobilevit: also time the fused forward with the attention core as one fused launch "
                          "(models.mobile_vit.NATIVE_ATTENTION) beside the torch attention, eager or with --graph "
                          "replayed from a graph each, the two arms alternating over --runs timed runs")
+    ap.add_argument("--native-ffn", action="store_true",
+                    help="fp32 mobilevit: also time the fused forward with LayerNorm + MLP + residual of every "
+                         "transformer layer as one fused launch (models.mobile_vit.NATIVE_FFN); with "
+                         "--native-attention a third arm with both switches on, the attention-only arm its baseline")
     args = ap.parse_args()
     if args.dtype == "bf16":
         return bench_bf16(args)
@@ -182,25 +188,32 @@ def main():
             t = timed(g.replay, args.steps * 4, args.warmup)
             res["graph_fused_ms"] = round(t * 1e3, 3)
             res["graph_fused_images_per_s"] = round(args.batch / t, 1)
-        if args.native_attention:
-            # the same fused forward, torch attention against the fused attention core, in alternating timed runs
+        if args.native_attention or args.native_ffn:
+            # the same fused forward with the transformer layers on torch ops against the fused attention core and / or
+            # the fused MLP, in alternating timed runs; each arm's logits against the first (all-torch) arm's
             quantized_conv.INFERENCE_FUSION = True
-            saved = mobile_vit.NATIVE_ATTENTION
+            saved = mobile_vit.NATIVE_ATTENTION, mobile_vit.NATIVE_FFN
+            arms = {"torch_attention": (False, False)}
+            if args.native_attention:
+                arms["native_attention"] = (True, False)
+            if args.native_ffn:
+                arms["native_attention_ffn" if args.native_attention else "native_ffn"] = (args.native_attention, True)
             try:
-                fns = {}
-                for name, on in (("torch_attention", False), ("native_attention", True)):
-                    mobile_vit.NATIVE_ATTENTION = on
-                    res[name + "_logits"] = m(x)
-                    fns[name] = capture().replay if args.graph else (lambda on=on: m(x))
+                fns, logits = {}, {}
+                for name, sw in arms.items():
+                    mobile_vit.NATIVE_ATTENTION, mobile_vit.NATIVE_FFN = sw
+                    logits[name] = m(x)
+                    fns[name] = capture().replay if args.graph else (lambda: m(x))
                 runs = {name: [] for name in fns}
                 for _ in range(args.runs):
                     for name, fn in fns.items():
-                        mobile_vit.NATIVE_ATTENTION = name == "native_attention"
+                        mobile_vit.NATIVE_ATTENTION, mobile_vit.NATIVE_FFN = arms[name]
                         runs[name].append(timed(fn, args.steps * (4 if args.graph else 1), args.warmup) * 1e3)
             finally:
-                mobile_vit.NATIVE_ATTENTION = saved
-            ref, got = res.pop("torch_attention_logits"), res.pop("native_attention_logits")
-            res["native_attention_vs_torch_normwise"] = float((got - ref).abs().max() / ref.abs().max())
+                mobile_vit.NATIVE_ATTENTION, mobile_vit.NATIVE_FFN = saved
+            ref = logits["torch_attention"]
+            for name in list(arms)[1:]:
+                res[name + "_vs_torch_normwise"] = float((logits[name] - ref).abs().max() / ref.abs().max())
             res["attention_arms_graph"] = bool(args.graph)
             for name, v in runs.items():
                 res[name + "_runs_ms"] = [round(t, 3) for t in v]
