@@ -387,6 +387,29 @@ int po2q_ffn_f32(const float* x, const float* ln_w, const float* ln_b, float eps
                  float* out, int M, int dim, int hidden, int residual, int kernel, void* stream);
 
 /*
+ * Fused LayerNorm + Linear + residual, fp32, forward only: the two halves of Attention around the attention core
+ * (reference models/mobile_vit.py:68-98 to_qkv(norm(x)) and to_out, and the add of Transformer.forward :108):
+ *   out[m, :] = [residual[m, :] +] (LN(x[m, :]) or x[m, :]) . W^T [+ bias]        per token m
+ * LN = LayerNorm over in_dim with weight ln_w, bias ln_b and eps: ln_w and ln_b are both NULL (no LayerNorm) or
+ * both non-NULL.  bias [out_dim] and residual [M, out_dim] may each be NULL.  x [M, in_dim], out [M, out_dim]
+ * contiguous; w [out_dim, in_dim] row-major as nn.Linear.weight stores it (nothing is transposed or packed on the
+ * host).  One launch on fp32 MFMA (exact products, fp32 accumulation).
+ * kernel: PO2Q_LNLIN_AUTO picks by M alone; PO2Q_LNLIN_RESIDENT (many tokens: a block keeps its rows of W in LDS
+ * and its waves stream 16-token tiles past them) and PO2Q_LNLIN_OUT_SPLIT (few tokens: a block is 16 tokens, its
+ * waves split the outputs) force one; both take every supported shape.
+ * Supported: M >= 1; in_dim % 4 == 0 and 4 <= in_dim <= PO2Q_LNLIN_MAX_IN (the largest multiple of 16 at which
+ * every instance of both kernels compiles for gfx950 without scratch memory: 640); out_dim % 4 == 0 and out_dim >= 4;
+ * x, w, out non-NULL; every non-NULL pointer 16-byte aligned; out overlaps neither x nor residual.  Anything else
+ * returns PO2Q_ERR_INVALID before any launch -- there is no other path inside the library.  Asynchronous, no
+ * workspace, allocates nothing, safe under graph capture.
+ */
+enum po2q_lnlin_kernel { PO2Q_LNLIN_AUTO = 0, PO2Q_LNLIN_RESIDENT = 1, PO2Q_LNLIN_OUT_SPLIT = 2 };
+#define PO2Q_LNLIN_MAX_IN 640
+int po2q_ln_linear_f32(const float* x, const float* ln_w, const float* ln_b, float eps,
+                       const float* w, const float* bias, const float* residual, float* out,
+                       int M, int in_dim, int out_dim, int kernel, void* stream);
+
+/*
  * Kernel autotuning, the counterpart of the reference's
  * torch.backends.cudnn.benchmark = True (train.py:33, test.py:31): times every
  * candidate plan for this problem on these buffers (synchronises the stream;

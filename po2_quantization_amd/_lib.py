@@ -87,6 +87,7 @@ EXPORTS = (
     "po2q_qconv2d_pair_bf16_describe",
     "po2q_mhsa_f32",
     "po2q_ffn_f32",
+    "po2q_ln_linear_f32",
 )
 
 # Kernel autotuning on the first call per conv problem, the counterpart of
@@ -247,6 +248,8 @@ def load():
     L.po2q_mhsa_f32.argtypes = [p, p, i32, i32, i32, i32, ctypes.c_float, p]
     L.po2q_ffn_f32.restype = i32
     L.po2q_ffn_f32.argtypes = [p, p, p, ctypes.c_float, p, p, p, p, p, i32, i32, i32, i32, i32, p]
+    L.po2q_ln_linear_f32.restype = i32
+    L.po2q_ln_linear_f32.argtypes = [p, p, p, ctypes.c_float, p, p, p, p, i32, i32, i32, i32, p]
     _lib = L
     return L
 
@@ -689,6 +692,40 @@ def ffn(x, ln_w, ln_b, eps, w1, b1, w2, b2, residual=True, kernel=0):
         _check(load().po2q_ffn_f32(x.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), float(eps), w1.data_ptr(),
                                    b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), out.data_ptr(), x.numel() // dim, dim,
                                    hidden, int(bool(residual)), int(kernel), _stream(x.device)))
+    return out
+
+
+def ln_linear(x, w, ln_w=None, ln_b=None, eps=1e-5, bias=None, residual=None, kernel=0):
+    """[residual +] Linear(LayerNorm(x) or x) in one launch (po2q_ln_linear_f32):
+    [residual +] (LN(x) or x) w^T [+ bias] per token -- to_qkv(norm(x)) and x + to_out(..) of Attention.  x [.., in_dim]
+    of rank >= 2, fp32, contiguous; w [out_dim, in_dim] as nn.Linear stores it; ln_w, ln_b [in_dim] (both or neither:
+    no LayerNorm), bias [out_dim] and residual [.., out_dim] are optional.  Returns [.., out_dim].  kernel: 0 picks by
+    the token count, 1 forces the weight-resident kernel, 2 the out-split kernel.  in_dim and out_dim are multiples of
+    4, in_dim <= 640; anything else raises.  Forward only."""
+    opt = ((ln_w, "ln_w"), (ln_b, "ln_b"), (bias, "bias"), (residual, "residual"))
+    for t, name in ((x, "x"), (w, "w")) + tuple(o for o in opt if o[0] is not None):
+        _require_hip_f32(t, name)
+    if x.dim() < 2:
+        raise Po2qError("po2q: ln_linear expects x of rank >= 2, got %d-D" % x.dim())
+    O = ops()
+    if O is not None:
+        return _op_call(O.ln_linear, x, ln_w, ln_b, float(eps), w, bias, residual, int(kernel))
+    in_dim, out_dim = x.shape[-1], w.shape[0]
+    shape = x.shape[:-1] + (out_dim,)
+    if (not all(t.is_contiguous() for t in (x, w) + tuple(o[0] for o in opt if o[0] is not None))
+            or tuple(w.shape) != (out_dim, in_dim) or (ln_w is None) != (ln_b is None)
+            or (ln_w is not None and not ln_w.numel() == ln_b.numel() == in_dim)
+            or (bias is not None and bias.numel() != out_dim) or (residual is not None and residual.shape != shape)):
+        raise Po2qError("po2q: ln_linear needs contiguous tensors: x [.., in_dim], w [out_dim, in_dim], ln_w and ln_b "
+                        "[in_dim] together or neither, bias [out_dim], residual [.., out_dim]")
+    out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    if out.numel() == 0:
+        return out
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(x.device):
+        _check(load().po2q_ln_linear_f32(x.data_ptr(), ptr(ln_w), ptr(ln_b), float(eps), w.data_ptr(), ptr(bias),
+                                         ptr(residual), out.data_ptr(), out.numel() // out_dim, in_dim, out_dim,
+                                         int(kernel), _stream(x.device)))
     return out
 
 

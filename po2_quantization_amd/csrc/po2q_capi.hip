@@ -889,6 +889,56 @@ int po2q_ffn_f32(const float* x, const float* ln_w, const float* ln_b, float eps
     return hip_status(launch_ffn(a, kernel, reinterpret_cast<hipStream_t>(stream)), "ffn launch");
 }
 
+// ------------------------------------------------- LayerNorm + Linear + residual --
+int po2q_ln_linear_f32(const float* x, const float* ln_w, const float* ln_b, float eps, const float* w,
+                       const float* bias, const float* residual, float* out, int M, int in_dim, int out_dim,
+                       int kernel, void* stream) {
+    if (!x || !w || !out) {
+        set_error("po2q: null pointer");
+        return PO2Q_ERR_INVALID;
+    }
+    if (!ln_w != !ln_b) {
+        set_error("po2q: ln_linear takes ln_w and ln_b together or neither");
+        return PO2Q_ERR_INVALID;
+    }
+    if (M <= 0) {
+        set_error("po2q: ln_linear needs a positive M, got M = " + std::to_string(M));
+        return PO2Q_ERR_INVALID;
+    }
+    if (in_dim < 4 || in_dim % 4 || in_dim > PO2Q_LNLIN_MAX_IN) {
+        set_error("po2q: ln_linear takes in_dim % 4 == 0 with 4 <= in_dim <= " + std::to_string(PO2Q_LNLIN_MAX_IN) +
+                  ", got in_dim = " + std::to_string(in_dim));
+        return PO2Q_ERR_INVALID;
+    }
+    if (out_dim < 4 || out_dim % 4) {
+        set_error("po2q: ln_linear takes out_dim % 4 == 0 with out_dim >= 4, got out_dim = " +
+                  std::to_string(out_dim));
+        return PO2Q_ERR_INVALID;
+    }
+    if (kernel != PO2Q_LNLIN_AUTO && kernel != PO2Q_LNLIN_RESIDENT && kernel != PO2Q_LNLIN_OUT_SPLIT) {
+        set_error("po2q: ln_linear: unknown kernel " + std::to_string(kernel) +
+                  " (0 auto, 1 weight resident, 2 out split)");
+        return PO2Q_ERR_INVALID;
+    }
+    uintptr_t bits = 0;  // a null pointer adds none
+    for (const void* q : {(const void*)x, (const void*)ln_w, (const void*)ln_b, (const void*)w, (const void*)bias,
+                          (const void*)residual, (const void*)out})
+        bits |= reinterpret_cast<uintptr_t>(q);
+    if (bits & 15) {
+        set_error("po2q: ln_linear needs 16-byte aligned pointers");
+        return PO2Q_ERR_INVALID;
+    }
+    const uintptr_t ob = reinterpret_cast<uintptr_t>(out), obytes = (uintptr_t)M * out_dim * sizeof(float);
+    const uintptr_t xb = reinterpret_cast<uintptr_t>(x), rb = reinterpret_cast<uintptr_t>(residual);
+    if ((xb < ob + obytes && ob < xb + (uintptr_t)M * in_dim * sizeof(float)) ||
+        (residual && rb < ob + obytes && ob < rb + obytes)) {
+        set_error("po2q: ln_linear: out must not overlap x or residual");
+        return PO2Q_ERR_INVALID;
+    }
+    const LnLinArgs a{x, ln_w, ln_b, w, bias, residual, out, M, in_dim, out_dim, eps};
+    return hip_status(launch_ln_linear(a, kernel, reinterpret_cast<hipStream_t>(stream)), "ln_linear launch");
+}
+
 int po2q_bf16_set_row_kernels(int on) { return b16_rows_set(on); }
 
 int po2q_bf16_row_kernels(void) { return b16_rows_get(); }

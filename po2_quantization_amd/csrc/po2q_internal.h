@@ -371,6 +371,17 @@ struct FfnArgs {
 };
 hipError_t launch_ffn(const FfnArgs& a, int kernel, hipStream_t s);
 
+// Fused LayerNorm + Linear + residual (po2q_lnlin.hip; po2q_ln_linear_f32): out = [residual +] (LN(x) or x) W^T
+// [+ bias] per token.  ln_w / ln_b (both or neither), bias and residual may be null.  kernel: a po2q_lnlin_kernel
+// value; the C entry has checked every argument (in_dim <= PO2Q_LNLIN_MAX_IN included).
+struct LnLinArgs {
+    const float *x, *ln_w, *ln_b, *w, *bias, *residual;
+    float* out;
+    int M, in_dim, out_dim;
+    float eps;
+};
+hipError_t launch_ln_linear(const LnLinArgs& a, int kernel, hipStream_t s);
+
 // lin / lin+ quantizer (po2q_lin.hip): w, out [d0, d1, rs = d2*d3], one block per d1 channel
 hipError_t launch_quantize_lin(const float* w, float* out, int d0, int d1, int rs, int bits, int num_iters, int plus,
                                hipStream_t s);

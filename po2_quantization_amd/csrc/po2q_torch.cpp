@@ -36,6 +36,8 @@
 //                        (mobile_vit.py:68-98) in one launch (po2q_mhsa_f32); forward only
 //   po2q::ffn            x + FeedForward(x) of a transformer layer (LayerNorm, Linear, SiLU, Linear, add) in one
 //                        launch (po2q_ffn_f32); forward only
+//   po2q::ln_linear      [residual +] Linear(LayerNorm(x) or x): to_qkv(norm(x)) and x + to_out(..) of Attention
+//                        (mobile_vit.py:68-98), each in one launch (po2q_ln_linear_f32); forward only
 // Meta kernels give the output shapes (FX / torch.compile tracing, fake tensors).
 // Errors are TORCH_CHECK -> RuntimeError, as F.conv2d raises for bad arguments.
 #include <ATen/ATen.h>
@@ -500,6 +502,62 @@ at::Tensor ffn_meta(const at::Tensor& x, const at::Tensor&, const at::Tensor&, d
                     const at::Tensor&, const at::Tensor&, const at::Tensor&, bool, int64_t) {
     ffn_check_x(x);
     return at::empty(x.sizes(), x.options());
+}
+
+// ---- fused LayerNorm + Linear + residual (po2q_ln_linear_f32): x [.., in_dim] -> [.., out_dim] ----
+// x and residual of any rank >= 2, contiguous; the parameters as nn.LayerNorm / nn.Linear store them; no copy is
+// made here.  The dtype and shape checks are shared with the Meta kernel; returns the output shape.
+using OptTensor = c10::optional<at::Tensor>;
+
+std::vector<int64_t> ln_linear_out_shape(const at::Tensor& x, const OptTensor& ln_w, const OptTensor& ln_b,
+                                         const at::Tensor& w, const OptTensor& bias, const OptTensor& residual) {
+    TORCH_CHECK(x.dim() >= 2, "po2q: ln_linear expects x of rank >= 2, got ", x.dim(), "-D");
+    TORCH_CHECK(ln_w.has_value() == ln_b.has_value(), "po2q: ln_linear takes ln_w and ln_b together or neither");
+    const at::Tensor* all[] = {&x, &w, ln_w ? &*ln_w : nullptr, ln_b ? &*ln_b : nullptr, bias ? &*bias : nullptr,
+                               residual ? &*residual : nullptr};
+    const char* names[] = {"x", "w", "ln_w", "ln_b", "bias", "residual"};
+    for (int i = 0; i < 6; ++i) {
+        if (!all[i]) continue;
+        TORCH_CHECK(all[i]->scalar_type() == at::kFloat, "po2q: ln_linear: ", names[i], " must be float32 (got ",
+                    all[i]->scalar_type(), ")");
+        TORCH_CHECK(all[i]->is_contiguous(), "po2q: ln_linear needs a contiguous ", names[i]);
+        TORCH_CHECK(all[i]->device() == x.device(), "po2q: ln_linear: ", names[i], " is on another device than x");
+    }
+    const int64_t in_dim = x.size(-1);
+    TORCH_CHECK(w.dim() == 2 && w.size(1) == in_dim, "po2q: ln_linear: w must be [out_dim, ", in_dim, "], got ",
+                w.sizes());
+    const int64_t out_dim = w.size(0);
+    TORCH_CHECK(!ln_w || (ln_w->numel() == in_dim && ln_b->numel() == in_dim),
+                "po2q: ln_linear: ln_w and ln_b must hold in_dim = ", in_dim, " values");
+    TORCH_CHECK(!bias || bias->numel() == out_dim, "po2q: ln_linear: bias must hold out_dim = ", out_dim,
+                " values, got ", bias ? bias->numel() : 0);
+    std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
+    shape.back() = out_dim;
+    TORCH_CHECK(!residual || residual->sizes() == at::IntArrayRef(shape), "po2q: ln_linear: residual must be ",
+                at::IntArrayRef(shape), ", got ", residual ? residual->sizes() : at::IntArrayRef());
+    return shape;
+}
+
+at::Tensor ln_linear(const at::Tensor& x, const OptTensor& ln_w, const OptTensor& ln_b, double eps,
+                     const at::Tensor& w, const OptTensor& bias, const OptTensor& residual, int64_t kernel) {
+    check_hip_f32(x, "x");
+    const std::vector<int64_t> shape = ln_linear_out_shape(x, ln_w, ln_b, w, bias, residual);
+    const int64_t in_dim = x.size(-1), out_dim = w.size(0), M = in_dim ? x.numel() / in_dim : 0;
+    TORCH_CHECK(M <= INT32_MAX && in_dim <= INT32_MAX && out_dim <= INT32_MAX, "po2q: ln_linear: M = ", M,
+                " / in_dim = ", in_dim, " / out_dim = ", out_dim, " out of range");
+    const DeviceGuard guard(x.device());
+    at::Tensor out = at::empty(shape, x.options());
+    if (out.numel() == 0) return out;
+    const int st = po2q_ln_linear_f32(x.data_ptr<float>(), opt_ptr(ln_w), opt_ptr(ln_b), (float)eps,
+                                      w.data_ptr<float>(), opt_ptr(bias), opt_ptr(residual), out.data_ptr<float>(),
+                                      (int)M, (int)in_dim, (int)out_dim, (int)kernel, stream_of(x));
+    TORCH_CHECK(st == 0, last_error());
+    return out;
+}
+
+at::Tensor ln_linear_meta(const at::Tensor& x, const OptTensor& ln_w, const OptTensor& ln_b, double,
+                          const at::Tensor& w, const OptTensor& bias, const OptTensor& residual, int64_t) {
+    return at::empty(ln_linear_out_shape(x, ln_w, ln_b, w, bias, residual), x.options());
 }
 
 // ---- batched weight staging of the bf16 forward (po2q_qconv2d_bf16_pack_batch / _packed_bf16) ----
@@ -1215,6 +1273,8 @@ TORCH_LIBRARY(po2q, m) {
     m.def("mhsa(Tensor qkv, int heads, float scale) -> Tensor");
     m.def("ffn(Tensor x, Tensor ln_w, Tensor ln_b, float eps, Tensor w1, Tensor b1, Tensor w2, Tensor b2, "
           "bool residual, int kernel) -> Tensor");
+    m.def("ln_linear(Tensor x, Tensor? ln_w, Tensor? ln_b, float eps, Tensor w, Tensor? bias, Tensor? residual, "
+          "int kernel) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(po2q, CUDA, m) {  // the HIP device (PyTorch-ROCm dispatches HIP tensors under CUDA)
@@ -1237,6 +1297,7 @@ TORCH_LIBRARY_IMPL(po2q, CUDA, m) {  // the HIP device (PyTorch-ROCm dispatches 
     m.impl("qconv2d_pair_bf16", &qconv2d_pair_bf16);
     m.impl("mhsa", &mhsa);
     m.impl("ffn", &ffn);
+    m.impl("ln_linear", &ln_linear);
 }
 
 TORCH_LIBRARY_IMPL(po2q, Meta, m) {
@@ -1259,4 +1320,5 @@ TORCH_LIBRARY_IMPL(po2q, Meta, m) {
     m.impl("qconv2d_pair_bf16", &qconv2d_pair_bf16_meta);
     m.impl("mhsa", &mhsa_meta);
     m.impl("ffn", &ffn_meta);
+    m.impl("ln_linear", &ln_linear_meta);
 }

@@ -15,8 +15,9 @@ The module tree reproduces the reference's nesting, so state_dict keys match:
 Only the QuantizedConv2d layers are quantized (the reference quantizes no
 Linear / attention weight, :56-128); attention, LayerNorm and the MLP stay
 plain torch ops -- they are off the graded path -- except that NATIVE_ATTENTION
-(below) runs the attention core as one fused launch, and NATIVE_FFN each
-layer's x + FeedForward(x) as another.  nxn convs use padding 1 as
+(below) runs the attention core as one fused launch, NATIVE_FFN each
+layer's x + FeedForward(x) as another, and NATIVE_PROJ the two projections
+around the core as one launch each.  nxn convs use padding 1 as
 in the reference (:32), whatever kernel_size is.  einops' rearranges are
 spelled as view/permute (same element order).
 
@@ -43,6 +44,12 @@ NATIVE_ATTENTION = os.environ.get("PO2Q_NATIVE_ATTENTION") == "1"
 # Linear, SiLU, Linear and the add) as one fused launch, _lib.ffn (po2q_ffn_f32).  PO2Q_NATIVE_FFN=1 sets it at
 # import; ptq.py --native-ffn and tools/model_bench.py --native-ffn set it for a run.
 NATIVE_FFN = os.environ.get("PO2Q_NATIVE_FFN") == "1"
+
+# Opt-in, independent of the two above: the same forwards run the projections on both sides of the attention core as
+# one fused launch each, _lib.ln_linear (po2q_ln_linear_f32): to_qkv(norm(x)), and to_out with the add of
+# Transformer.forward (x + attn(x)) in its store.  PO2Q_NATIVE_PROJ=1 sets it at import; ptq.py --native-proj and
+# tools/model_bench.py --native-proj set it for a run.
+NATIVE_PROJ = os.environ.get("PO2Q_NATIVE_PROJ") == "1"
 
 
 def quantized_conv_1x1_bn(inp, oup, quantize_fn=None, bits=4):
@@ -87,18 +94,34 @@ class Attention(nn.Module):
         self.to_qkv = nn.Linear(dim, 3 * heads * dim_head, bias=False)
         self.to_out = nn.Sequential(nn.Linear(heads * dim_head, dim), nn.Dropout(dropout))
 
-    def forward(self, x):
+    def forward(self, x, add_input=False):
+        """attention(x), or x + attention(x) with add_input (what Transformer.forward wants)."""
         b, p, n, _ = x.shape
-        qkv = self.to_qkv(self.norm(x))
+        proj = (NATIVE_PROJ and x.device.type == "cuda" and x.dtype == torch.float32
+                and not (self.training and self.dropout.p > 0)
+                and not (torch.is_grad_enabled() and (x.requires_grad or any(w.requires_grad
+                                                                             for w in self.parameters()))))
+        if proj:
+            # fp32 HIP forward with no gradient recorded and no active dropout: LayerNorm + to_qkv as one launch
+            # (1x1 patches hand in a strided view: the kernel reads rows, so the block's first layer copies once)
+            x = x.contiguous()
+            qkv = _lib.ln_linear(x, self.to_qkv.weight, self.norm.weight, self.norm.bias, self.norm.eps)
+        else:
+            qkv = self.to_qkv(self.norm(x))
         if (NATIVE_ATTENTION and qkv.device.type == "cuda" and qkv.dtype == torch.float32 and not qkv.requires_grad
                 and not (self.training and self.dropout.p > 0)):
             # fp32 HIP forward with no gradient recorded and no active dropout: one fused launch, no copies
-            return self.to_out(_lib.mhsa(qkv, self.heads, self.scale))
-        # [b, p, n, 3*h*d] -> q, k, v each [b, p, h, n, d]
-        q, k, v = (t.view(b, p, n, self.heads, -1).transpose(2, 3) for t in qkv.chunk(3, dim=-1))
-        attn = self.dropout(self.attend(torch.matmul(q, k.transpose(-1, -2)) * self.scale))
-        out = torch.matmul(attn, v).transpose(2, 3).reshape(b, p, n, -1)
-        return self.to_out(out)
+            out = _lib.mhsa(qkv, self.heads, self.scale)
+        else:
+            # [b, p, n, 3*h*d] -> q, k, v each [b, p, h, n, d]
+            q, k, v = (t.view(b, p, n, self.heads, -1).transpose(2, 3) for t in qkv.chunk(3, dim=-1))
+            attn = self.dropout(self.attend(torch.matmul(q, k.transpose(-1, -2)) * self.scale))
+            out = torch.matmul(attn, v).transpose(2, 3).reshape(b, p, n, -1)
+        if proj:  # to_out and the add in one launch
+            fc = self.to_out[0]
+            return _lib.ln_linear(out, fc.weight, bias=fc.bias, residual=x if add_input else None)
+        out = self.to_out(out)
+        return x + out if add_input else out
 
 
 class Transformer(nn.Module):
@@ -110,7 +133,7 @@ class Transformer(nn.Module):
 
     def forward(self, x):
         for attn, ff in self.layers:
-            x = x + attn(x)
+            x = attn(x, add_input=True)
             if (NATIVE_FFN and x.device.type == "cuda" and x.dtype == torch.float32 and not x.requires_grad
                     and not (ff.training and ff.net[3].p > 0)):
                 # fp32 HIP forward with no gradient recorded and no active dropout: one fused launch

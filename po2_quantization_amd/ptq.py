@@ -151,7 +151,7 @@ def main(model_type: str, dataset: str, data_file: str, batch_size: int = 128, t
          results_dir: str = "./results", skip_qat: bool = False, dtype: str = "fp32",
          bf16_fused_epilogue: bool = False, bf16_row_kernels: bool = False,
          bf16_rowsk_kernels: bool = False, bf16_pairs: bool = False, native_attention: bool = False,
-         native_ffn: bool = False) -> None:
+         native_ffn: bool = False, native_proj: bool = False) -> None:
     """test.py:58-164 with the evaluation set from data_file."""
     assert dtype in DTYPES, "invalid dtype"
     assert not bf16_fused_epilogue or dtype == "bf16", "--bf16-fused-epilogue needs --dtype bf16"
@@ -178,6 +178,8 @@ def main(model_type: str, dataset: str, data_file: str, batch_size: int = 128, t
     mobile_vit.NATIVE_ATTENTION = bool(native_attention) or saved_attention  # for this run
     saved_ffn = mobile_vit.NATIVE_FFN
     mobile_vit.NATIVE_FFN = bool(native_ffn) or saved_ffn  # for this run
+    saved_proj = mobile_vit.NATIVE_PROJ
+    mobile_vit.NATIVE_PROJ = bool(native_proj) or saved_proj  # for this run
     saved_rows = _lib.set_bf16_row_kernels(bool(bf16_row_kernels))  # for this run
     saved_rowsk = _lib.set_bf16_rowsk_kernels(bool(bf16_rowsk_kernels))  # for this run
     try:
@@ -191,6 +193,7 @@ def main(model_type: str, dataset: str, data_file: str, batch_size: int = 128, t
         quantized_conv.BF16_PAIRS = saved_pairs
         mobile_vit.NATIVE_ATTENTION = saved_attention
         mobile_vit.NATIVE_FFN = saved_ffn
+        mobile_vit.NATIVE_PROJ = saved_proj
         _lib.set_bf16_row_kernels(saved_rows)
         _lib.set_bf16_rowsk_kernels(saved_rowsk)
 
@@ -220,6 +223,9 @@ def arg_parser():
     ap.add_argument("--native-ffn", action="store_true",
                     help="mobilevit in fp32: LayerNorm + MLP + residual of every transformer layer as one fused launch "
                          "(models.mobile_vit.NATIVE_FFN), for this run")
+    ap.add_argument("--native-proj", action="store_true",
+                    help="mobilevit in fp32: LayerNorm + to_qkv and to_out + residual of every transformer layer as one "
+                         "fused launch each (models.mobile_vit.NATIVE_PROJ), for this run")
     ap.add_argument("--bf16-row-kernels", action="store_true",
                     help="with --dtype bf16: the row-streaming conv kernel for the 3x3 stride-1 C = K = 16 / 32 "
                          "layers (_lib.set_bf16_row_kernels), for this run")
@@ -233,4 +239,4 @@ if __name__ == "__main__":
     a = arg_parser().parse_args()
     main(a.model_type, a.dataset, a.data_file, a.batch_size, a.train_dir, a.results_dir, a.skip_qat, a.dtype,
          a.bf16_fused_epilogue, a.bf16_row_kernels, a.bf16_rowsk_kernels, a.bf16_pairs, a.native_attention,
-         a.native_ffn)
+         a.native_ffn, a.native_proj)

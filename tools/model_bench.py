@@ -22,7 +22,9 @@ The fp32 fused forward of MobileViT with the torch attention core against the fu
 NATIVE_ATTENTION, po2q_mhsa_f32): both arms in one process, as captured graphs with --graph, timed in alternating runs;
 every run's milliseconds per arm, the spread within an arm and the logits' normwise difference join the JSON line.
 --native-ffn adds an arm with the fused LayerNorm + MLP + residual launch (models.mobile_vit.NATIVE_FFN, po2q_ffn_f32):
-on top of the fused attention when --native-attention is given too, on the torch attention otherwise."""
+on top of the fused attention when --native-attention is given too, on the torch attention otherwise.  --native-proj
+adds one more arm with LayerNorm + to_qkv and to_out + residual as one launch each (models.mobile_vit.NATIVE_PROJ,
+po2q_ln_linear_f32) on top of whichever of the other two switches are given."""
 import argparse
 import json
 import os
@@ -148,6 +150,10 @@ def main():
                     help="fp32 mobilevit: also time the fused forward with LayerNorm + MLP + residual of every "
                          "transformer layer as one fused launch (models.mobile_vit.NATIVE_FFN); with "
                          "--native-attention a third arm with both switches on, the attention-only arm its baseline")
+    ap.add_argument("--native-proj", action="store_true",
+                    help="fp32 mobilevit: also time the fused forward with LayerNorm + to_qkv and to_out + residual of "
+                         "every transformer layer as one fused launch each (models.mobile_vit.NATIVE_PROJ), on top of "
+                         "the other two switches that are given; that arm without it is its baseline")
     args = ap.parse_args()
     if args.dtype == "bf16":
         return bench_bf16(args)
@@ -188,29 +194,34 @@ def main():
             t = timed(g.replay, args.steps * 4, args.warmup)
             res["graph_fused_ms"] = round(t * 1e3, 3)
             res["graph_fused_images_per_s"] = round(args.batch / t, 1)
-        if args.native_attention or args.native_ffn:
-            # the same fused forward with the transformer layers on torch ops against the fused attention core and / or
-            # the fused MLP, in alternating timed runs; each arm's logits against the first (all-torch) arm's
+        if args.native_attention or args.native_ffn or args.native_proj:
+            # the same fused forward with the transformer layers on torch ops against the fused attention core, the
+            # fused MLP and / or the fused projections, in alternating timed runs; each arm's logits against the first
+            # (all-torch) arm's
             quantized_conv.INFERENCE_FUSION = True
-            saved = mobile_vit.NATIVE_ATTENTION, mobile_vit.NATIVE_FFN
-            arms = {"torch_attention": (False, False)}
+            saved = mobile_vit.NATIVE_ATTENTION, mobile_vit.NATIVE_FFN, mobile_vit.NATIVE_PROJ
+            arms = {"torch_attention": (False, False, False)}
             if args.native_attention:
-                arms["native_attention"] = (True, False)
+                arms["native_attention"] = (True, False, False)
             if args.native_ffn:
-                arms["native_attention_ffn" if args.native_attention else "native_ffn"] = (args.native_attention, True)
+                arms["native_attention_ffn" if args.native_attention else "native_ffn"] = (args.native_attention, True,
+                                                                                         False)
+            if args.native_proj:
+                on = [n for n, v in (("attention", args.native_attention), ("ffn", args.native_ffn)) if v]
+                arms["_".join(["native"] + on + ["proj"])] = (args.native_attention, args.native_ffn, True)
             try:
                 fns, logits = {}, {}
                 for name, sw in arms.items():
-                    mobile_vit.NATIVE_ATTENTION, mobile_vit.NATIVE_FFN = sw
+                    mobile_vit.NATIVE_ATTENTION, mobile_vit.NATIVE_FFN, mobile_vit.NATIVE_PROJ = sw
                     logits[name] = m(x)
                     fns[name] = capture().replay if args.graph else (lambda: m(x))
                 runs = {name: [] for name in fns}
                 for _ in range(args.runs):
                     for name, fn in fns.items():
-                        mobile_vit.NATIVE_ATTENTION, mobile_vit.NATIVE_FFN = arms[name]
+                        mobile_vit.NATIVE_ATTENTION, mobile_vit.NATIVE_FFN, mobile_vit.NATIVE_PROJ = arms[name]
                         runs[name].append(timed(fn, args.steps * (4 if args.graph else 1), args.warmup) * 1e3)
             finally:
-                mobile_vit.NATIVE_ATTENTION, mobile_vit.NATIVE_FFN = saved
+                mobile_vit.NATIVE_ATTENTION, mobile_vit.NATIVE_FFN, mobile_vit.NATIVE_PROJ = saved
             ref = logits["torch_attention"]
             for name in list(arms)[1:]:
                 res[name + "_vs_torch_normwise"] = float((logits[name] - ref).abs().max() / ref.abs().max())
