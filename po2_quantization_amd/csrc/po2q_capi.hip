@@ -47,6 +47,29 @@ int hip_status(hipError_t e, const char* what) {
     return PO2Q_ERR_HIP;
 }
 
+// The argument checks the fp32 transformer entries (mhsa, ffn, ln_linear) share.
+int invalid(const std::string& msg) {
+    set_error(msg);
+    return PO2Q_ERR_INVALID;
+}
+
+bool any_null(std::initializer_list<const void*> ptrs) {
+    return std::any_of(ptrs.begin(), ptrs.end(), [](const void* q) { return !q; });
+}
+
+bool misaligned16(std::initializer_list<const void*> ptrs) {  // a null pointer adds no bits
+    uintptr_t bits = 0;
+    for (const void* q : ptrs) bits |= reinterpret_cast<uintptr_t>(q);
+    return (bits & 15) != 0;
+}
+
+bool bad_dim(int v, int max) { return v < 4 || v % 4 || v > max; }  // not "v % 4 == 0 with 4 <= v <= max"
+
+bool ranges_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
+    const uintptr_t ab = reinterpret_cast<uintptr_t>(a), bb = reinterpret_cast<uintptr_t>(b);
+    return ab < bb + bbytes && bb < ab + abytes;
+}
+
 }  // namespace
 
 extern "C" {
@@ -825,23 +848,13 @@ int po2q_qconv2d_pair_bf16_describe(int64_t N, int64_t C, int64_t H, int64_t W, 
 
 // ------------------------------------------------------------------ attention core --
 int po2q_mhsa_f32(const float* qkv, float* out, int S, int N, int heads, int dim_head, float scale, void* stream) {
-    if (!qkv || !out) {
-        set_error("po2q: null pointer");
-        return PO2Q_ERR_INVALID;
-    }
-    if (S <= 0 || N <= 0 || N > INT32_MAX - 16) {
-        set_error("po2q: mhsa needs positive S and N, got S = " + std::to_string(S) + ", N = " + std::to_string(N));
-        return PO2Q_ERR_INVALID;
-    }
-    if (!mhsa_supported(heads, dim_head)) {
-        set_error("po2q: mhsa takes heads == 4 and dim_head == 8, got heads = " + std::to_string(heads) +
-                  ", dim_head = " + std::to_string(dim_head));
-        return PO2Q_ERR_INVALID;
-    }
-    if ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(out)) & 15) {
-        set_error("po2q: mhsa needs 16-byte aligned qkv and out");
-        return PO2Q_ERR_INVALID;
-    }
+    if (any_null({qkv, out})) return invalid("po2q: null pointer");
+    if (S <= 0 || N <= 0 || N > INT32_MAX - 16)
+        return invalid("po2q: mhsa needs positive S and N, got S = " + std::to_string(S) + ", N = " + std::to_string(N));
+    if (!mhsa_supported(heads, dim_head))
+        return invalid("po2q: mhsa takes heads == 4 and dim_head == 8, got heads = " + std::to_string(heads) +
+                       ", dim_head = " + std::to_string(dim_head));
+    if (misaligned16({qkv, out})) return invalid("po2q: mhsa needs 16-byte aligned qkv and out");
     return hip_status(launch_mhsa(qkv, out, S, N, scale, reinterpret_cast<hipStream_t>(stream)), "mhsa launch");
 }
 
@@ -849,42 +862,19 @@ int po2q_mhsa_f32(const float* qkv, float* out, int S, int N, int heads, int dim
 int po2q_ffn_f32(const float* x, const float* ln_w, const float* ln_b, float eps, const float* w1, const float* b1,
                  const float* w2, const float* b2, float* out, int M, int dim, int hidden, int residual, int kernel,
                  void* stream) {
-    const void* ptrs[] = {x, ln_w, ln_b, w1, b1, w2, b2, out};
-    uintptr_t bits = 0;
-    for (const void* q : ptrs) {
-        if (!q) {
-            set_error("po2q: null pointer");
-            return PO2Q_ERR_INVALID;
-        }
-        bits |= reinterpret_cast<uintptr_t>(q);
-    }
-    if (M <= 0) {
-        set_error("po2q: ffn needs a positive M, got M = " + std::to_string(M));
-        return PO2Q_ERR_INVALID;
-    }
-    if (dim < 4 || dim % 4 || dim > PO2Q_FFN_MAX_DIM) {
-        set_error("po2q: ffn takes dim % 4 == 0 with 4 <= dim <= " + std::to_string(PO2Q_FFN_MAX_DIM) +
-                  ", got dim = " + std::to_string(dim));
-        return PO2Q_ERR_INVALID;
-    }
-    if (hidden < 4 || hidden % 4) {
-        set_error("po2q: ffn takes hidden % 4 == 0 with hidden >= 4, got hidden = " + std::to_string(hidden));
-        return PO2Q_ERR_INVALID;
-    }
-    if (kernel != PO2Q_FFN_AUTO && kernel != PO2Q_FFN_TOKEN_TILES && kernel != PO2Q_FFN_HIDDEN_SPLIT) {
-        set_error("po2q: ffn: unknown kernel " + std::to_string(kernel) + " (0 auto, 1 token tiles, 2 hidden split)");
-        return PO2Q_ERR_INVALID;
-    }
-    if (bits & 15) {
-        set_error("po2q: ffn needs 16-byte aligned pointers");
-        return PO2Q_ERR_INVALID;
-    }
-    const uintptr_t xb = reinterpret_cast<uintptr_t>(x), ob = reinterpret_cast<uintptr_t>(out);
-    const uintptr_t bytes = (uintptr_t)M * dim * sizeof(float);
-    if (xb < ob + bytes && ob < xb + bytes) {
-        set_error("po2q: ffn: out must not overlap x");
-        return PO2Q_ERR_INVALID;
-    }
+    if (any_null({x, ln_w, ln_b, w1, b1, w2, b2, out})) return invalid("po2q: null pointer");
+    if (M <= 0) return invalid("po2q: ffn needs a positive M, got M = " + std::to_string(M));
+    if (bad_dim(dim, PO2Q_FFN_MAX_DIM))
+        return invalid("po2q: ffn takes dim % 4 == 0 with 4 <= dim <= " + std::to_string(PO2Q_FFN_MAX_DIM) +
+                       ", got dim = " + std::to_string(dim));
+    if (bad_dim(hidden, INT32_MAX))
+        return invalid("po2q: ffn takes hidden % 4 == 0 with hidden >= 4, got hidden = " + std::to_string(hidden));
+    if (kernel != PO2Q_FFN_AUTO && kernel != PO2Q_FFN_TOKEN_TILES && kernel != PO2Q_FFN_HIDDEN_SPLIT)
+        return invalid("po2q: ffn: unknown kernel " + std::to_string(kernel) +
+                       " (0 auto, 1 token tiles, 2 hidden split)");
+    if (misaligned16({x, ln_w, ln_b, w1, b1, w2, b2, out})) return invalid("po2q: ffn needs 16-byte aligned pointers");
+    const size_t bytes = (size_t)M * dim * sizeof(float);
+    if (ranges_overlap(x, bytes, out, bytes)) return invalid("po2q: ffn: out must not overlap x");
     const FfnArgs a{x, ln_w, ln_b, w1, b1, w2, b2, out, M, dim, hidden, residual != 0, eps};
     return hip_status(launch_ffn(a, kernel, reinterpret_cast<hipStream_t>(stream)), "ffn launch");
 }
@@ -893,48 +883,24 @@ int po2q_ffn_f32(const float* x, const float* ln_w, const float* ln_b, float eps
 int po2q_ln_linear_f32(const float* x, const float* ln_w, const float* ln_b, float eps, const float* w,
                        const float* bias, const float* residual, float* out, int M, int in_dim, int out_dim,
                        int kernel, void* stream) {
-    if (!x || !w || !out) {
-        set_error("po2q: null pointer");
-        return PO2Q_ERR_INVALID;
-    }
-    if (!ln_w != !ln_b) {
-        set_error("po2q: ln_linear takes ln_w and ln_b together or neither");
-        return PO2Q_ERR_INVALID;
-    }
-    if (M <= 0) {
-        set_error("po2q: ln_linear needs a positive M, got M = " + std::to_string(M));
-        return PO2Q_ERR_INVALID;
-    }
-    if (in_dim < 4 || in_dim % 4 || in_dim > PO2Q_LNLIN_MAX_IN) {
-        set_error("po2q: ln_linear takes in_dim % 4 == 0 with 4 <= in_dim <= " + std::to_string(PO2Q_LNLIN_MAX_IN) +
-                  ", got in_dim = " + std::to_string(in_dim));
-        return PO2Q_ERR_INVALID;
-    }
-    if (out_dim < 4 || out_dim % 4) {
-        set_error("po2q: ln_linear takes out_dim % 4 == 0 with out_dim >= 4, got out_dim = " +
-                  std::to_string(out_dim));
-        return PO2Q_ERR_INVALID;
-    }
-    if (kernel != PO2Q_LNLIN_AUTO && kernel != PO2Q_LNLIN_RESIDENT && kernel != PO2Q_LNLIN_OUT_SPLIT) {
-        set_error("po2q: ln_linear: unknown kernel " + std::to_string(kernel) +
-                  " (0 auto, 1 weight resident, 2 out split)");
-        return PO2Q_ERR_INVALID;
-    }
-    uintptr_t bits = 0;  // a null pointer adds none
-    for (const void* q : {(const void*)x, (const void*)ln_w, (const void*)ln_b, (const void*)w, (const void*)bias,
-                          (const void*)residual, (const void*)out})
-        bits |= reinterpret_cast<uintptr_t>(q);
-    if (bits & 15) {
-        set_error("po2q: ln_linear needs 16-byte aligned pointers");
-        return PO2Q_ERR_INVALID;
-    }
-    const uintptr_t ob = reinterpret_cast<uintptr_t>(out), obytes = (uintptr_t)M * out_dim * sizeof(float);
-    const uintptr_t xb = reinterpret_cast<uintptr_t>(x), rb = reinterpret_cast<uintptr_t>(residual);
-    if ((xb < ob + obytes && ob < xb + (uintptr_t)M * in_dim * sizeof(float)) ||
-        (residual && rb < ob + obytes && ob < rb + obytes)) {
-        set_error("po2q: ln_linear: out must not overlap x or residual");
-        return PO2Q_ERR_INVALID;
-    }
+    if (any_null({x, w, out})) return invalid("po2q: null pointer");
+    if (!ln_w != !ln_b) return invalid("po2q: ln_linear takes ln_w and ln_b together or neither");
+    if (M <= 0) return invalid("po2q: ln_linear needs a positive M, got M = " + std::to_string(M));
+    if (bad_dim(in_dim, PO2Q_LNLIN_MAX_IN))
+        return invalid("po2q: ln_linear takes in_dim % 4 == 0 with 4 <= in_dim <= " +
+                       std::to_string(PO2Q_LNLIN_MAX_IN) + ", got in_dim = " + std::to_string(in_dim));
+    if (bad_dim(out_dim, INT32_MAX))
+        return invalid("po2q: ln_linear takes out_dim % 4 == 0 with out_dim >= 4, got out_dim = " +
+                       std::to_string(out_dim));
+    if (kernel != PO2Q_LNLIN_AUTO && kernel != PO2Q_LNLIN_RESIDENT && kernel != PO2Q_LNLIN_OUT_SPLIT)
+        return invalid("po2q: ln_linear: unknown kernel " + std::to_string(kernel) +
+                       " (0 auto, 1 weight resident, 2 out split)");
+    if (misaligned16({x, ln_w, ln_b, w, bias, residual, out}))
+        return invalid("po2q: ln_linear needs 16-byte aligned pointers");
+    const size_t obytes = (size_t)M * out_dim * sizeof(float);
+    if (ranges_overlap(x, (size_t)M * in_dim * sizeof(float), out, obytes) ||
+        (residual && ranges_overlap(residual, obytes, out, obytes)))
+        return invalid("po2q: ln_linear: out must not overlap x or residual");
     const LnLinArgs a{x, ln_w, ln_b, w, bias, residual, out, M, in_dim, out_dim, eps};
     return hip_status(launch_ln_linear(a, kernel, reinterpret_cast<hipStream_t>(stream)), "ln_linear launch");
 }

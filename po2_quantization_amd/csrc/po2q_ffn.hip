@@ -11,11 +11,9 @@
 //   * the accumulator is the next operand.  After + b1 and SiLU the lane holds H^T[4 g + r][tok], r = 0..3: the B
 //     operand of k-step r of Y^T[16 dim x 16 tok] += W2[dim tile, chunk] H^T once that k-step's A operand is
 //     W2[d = lane & 15][hid = 4 g + r] -- the lane's dwordx4 W2[d][16 c + 4 g .. + 3].  The hidden tile goes from
-//     one GEMM to the next in the lane's own registers: no LDS round trip, no shuffle (key_group's trick for P^T
-//     in po2q_mhsa.hip).
+//     one GEMM to the next in the lane's own registers: no LDS round trip, no shuffle.
 //   * Y^T[16 t + 4 g + r][tok] is the layout x was loaded in: bias, residual and one dwordx4 store per dim tile.
-//   * LayerNorm in registers: a token's dim values sit in the four lanes that share lane & 15; the mean and then
-//     the centred variance take two lane exchanges each (xor 16, xor 32).
+//   * the row load, the in-register LayerNorm and the store are the shared ones of po2q_vit_dev.h.
 //   * SiLU(h) = h * v_rcp_f32(1 + v_exp_f32(-h log2 e)): h -> -inf gives h * 0 = -0, h -> +inf gives h.
 //   * partial tiles (dim or hidden no multiple of 16, tokens >= M) run on zero operands; tokens >= M and dims
 //     >= dim are not stored.  dim % 4 == 0 and hidden % 4 == 0 keep every dwordx4 whole.
@@ -29,69 +27,26 @@
 //   hidden split (ffn_split_kernel, few tokens)  a block is ONE token tile; its 4 waves take the hidden chunks
 //       c = wave (mod 4) with operands straight from global memory (each weight is read once per block), the four
 //       partial Y^T are summed through LDS in wave order and each wave finishes the dim tiles t = wave (mod 4).
-#include <utility>
-
 #include "po2q.h"
 #include "po2q_internal.h"
+#include "po2q_vit_dev.h"
 
 namespace po2q {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kMaxT = PO2Q_FFN_MAX_DIM / 16;  // dim tiles of the widest supported dim
 constexpr int kP2 = 20;                       // LDS floats per W2 row (16 used)
 constexpr int kSplitMaxM = 16384;             // PO2Q_FFN_AUTO: the hidden-split kernel up to this many tokens
-constexpr float kLog2e = 1.44269504088896341f;
 
 constexpr int tiles_per_wave(int T) { return T <= 9 ? 2 : 1; }
 constexpr int w1_pitch(int T) { return 16 * T + 4; }
 constexpr int lds_buf_floats(int T) { return 16 * w1_pitch(T) + 16 * T * kP2; }  // one chunk: W1 rows, then W2 rows
 
-__device__ __forceinline__ f32x4 ld4(const float* p, bool ok) {
-    return ok ? *reinterpret_cast<const f32x4*>(p) : f32x4{0.f, 0.f, 0.f, 0.f};
-}
-
-__device__ __forceinline__ float quad_sum(float v) {  // over the four lanes that share lane & 15
-    v += __shfl_xor(v, 16);
-    return v + __shfl_xor(v, 32);
-}
-
-// xn[t] = LN(x[tok])[16 t + 4 g .. + 3], zeros past dim.  Only the last dim tile can be ragged (tail_ok: the lane's
-// part of it is inside dim).  A token >= M reads as zeros (LN of zeros is ln_b: finite, and never stored).
-template <int T>
-__device__ __forceinline__ void load_norm(f32x4 (&xn)[T], const FfnArgs& a, int64_t tok, int g, bool tail_ok) {
-    const float* xr = a.x + (size_t)tok * a.dim + 4 * g;
-    float s = 0.f;
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-        xn[t] = ld4(xr + 16 * t, tok < a.M && (t < T - 1 || tail_ok));
-        s += (xn[t][0] + xn[t][1]) + (xn[t][2] + xn[t][3]);
-    }
-    const float mean = quad_sum(s) / (float)a.dim;
-    float ss = 0.f;
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float d = (t < T - 1 || tail_ok) ? xn[t][r] - mean : 0.f;
-            xn[t][r] = d;
-            ss = fmaf(d, d, ss);
-        }
-    }
-    const float rstd = rsqrtf(quad_sum(ss) / (float)a.dim + a.eps);
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-        const bool ok = t < T - 1 || tail_ok;  // past dim: d = 0, w = b = 0
-        const f32x4 w = ld4(a.ln_w + 16 * t + 4 * g, ok), b = ld4(a.ln_b + 16 * t + 4 * g, ok);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) xn[t][r] = fmaf(xn[t][r] * rstd, w[r], b[r]);
-    }
-}
-
 // One chunk of 16 hidden units for the wave's TW token tiles.  w1op(t) / w2op(t) give the lane's A operands:
 // W1[16 c + (lane & 15)][16 t + 4 g .. + 3] and W2[16 t + (lane & 15)][16 c + 4 g .. + 3]; b1v = b1[16 c + 4 g .. + 3].
+// The k-steps of the TW token tiles are interleaved (independent accumulators back to back), so this is not mfma4:
+// one tile after the other costs the TW = 2 instances 4 more VGPRs.
 template <int T, int TW, class W1Op, class W2Op>
 __device__ __forceinline__ void hidden_chunk(const f32x4 (&xn)[TW][T], f32x4 (&acc)[TW][T], f32x4 b1v, W1Op w1op,
                                              W2Op w2op) {
@@ -124,16 +79,6 @@ __device__ __forceinline__ void hidden_chunk(const f32x4 (&xn)[TW][T], f32x4 (&a
     }
 }
 
-// out[tok][d0 .. + 3] = (y + b2) + x, y = Y^T[d0 .. + 3][tok]; d0 = 16 t + 4 g
-__device__ __forceinline__ void store_quad(const FfnArgs& a, f32x4 y, int64_t tok, int d0) {
-    if (tok < a.M && d0 < a.dim) {
-        y += *reinterpret_cast<const f32x4*>(a.b2 + d0);
-        const size_t at = (size_t)tok * a.dim + d0;
-        if (a.residual) y += *reinterpret_cast<const f32x4*>(a.x + at);
-        *reinterpret_cast<f32x4*>(a.out + at) = y;
-    }
-}
-
 template <int T, int TW>
 __global__ __launch_bounds__(256) void ffn_tiles_kernel(const FfnArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];  // 2 x [W1: 16 rows of P1 | W2: 16 T rows of kP2]
@@ -142,6 +87,7 @@ __global__ __launch_bounds__(256) void ffn_tiles_kernel(const FfnArgs a) {
     constexpr int PER = (T + 1) / 2;    // dwordx4 a thread stages per chunk (2 NV / 256, rounded up)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, g = lane >> 4;
     const int nch = (a.hidden + 15) >> 4;
+    __builtin_assume(a.x != nullptr && a.b2 != nullptr);  // checked by the C entry: store_quad branches on neither
     const bool tail_ok = 16 * (T - 1) + 4 * g < a.dim;
 
     f32x4 pre[PER];
@@ -175,7 +121,10 @@ __global__ __launch_bounds__(256) void ffn_tiles_kernel(const FfnArgs a) {
     f32x4 xn[TW][T], acc[TW][T];
 #pragma unroll
     for (int u = 0; u < TW; ++u) {
-        if (active) load_norm<T>(xn[u], a, tok0 + 16 * u, g, tail_ok);
+        if (active) {
+            load_tokens<T>(xn[u], a.x, a.M, a.dim, tok0 + 16 * u, g, tail_ok);
+            layer_norm<T>(xn[u], a.ln_w, a.ln_b, a.dim, a.eps, g, tail_ok);
+        }
 #pragma unroll
         for (int t = 0; t < T; ++t) acc[u][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
@@ -196,10 +145,11 @@ __global__ __launch_bounds__(256) void ffn_tiles_kernel(const FfnArgs a) {
         __syncthreads();
     }
     if (!active) return;
+    const float* res = a.residual ? a.x : nullptr;
 #pragma unroll
     for (int u = 0; u < TW; ++u)
 #pragma unroll
-        for (int t = 0; t < T; ++t) store_quad(a, acc[u][t], tok0 + 16 * u, 16 * t + 4 * g);
+        for (int t = 0; t < T; ++t) store_quad(a.out, acc[u][t], tok0 + 16 * u, a.M, 16 * t + 4 * g, a.dim, a.b2, res);
 }
 
 template <int T>
@@ -207,10 +157,12 @@ __global__ __launch_bounds__(256) void ffn_split_kernel(const FfnArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];  // the waves' partial Y^T: [4][T][64] dwordx4
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, g = lane >> 4;
     const int nch = (a.hidden + 15) >> 4;
+    __builtin_assume(a.x != nullptr && a.b2 != nullptr);  // checked by the C entry: store_quad branches on neither
     const bool tail_ok = 16 * (T - 1) + 4 * g < a.dim;
     const int64_t tok = (int64_t)blockIdx.x * 16 + l15;
     f32x4 xn[1][T], acc[1][T];
-    load_norm<T>(xn[0], a, tok, g, tail_ok);
+    load_tokens<T>(xn[0], a.x, a.M, a.dim, tok, g, tail_ok);
+    layer_norm<T>(xn[0], a.ln_w, a.ln_b, a.dim, a.eps, g, tail_ok);
 #pragma unroll
     for (int t = 0; t < T; ++t) acc[0][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int c = wave; c < nch; c += 4) {
@@ -230,43 +182,22 @@ __global__ __launch_bounds__(256) void ffn_split_kernel(const FfnArgs a) {
         f32x4 y = part[t * 64 + lane];
 #pragma unroll
         for (int w = 1; w < 4; ++w) y += part[(w * T + t) * 64 + lane];
-        store_quad(a, y, tok, 16 * t + 4 * g);
+        store_quad(a.out, y, tok, a.M, 16 * t + 4 * g, a.dim, a.b2, a.residual ? a.x : nullptr);
     }
-}
-
-template <class K>
-hipError_t launch(K kern, int64_t blocks, size_t lds_bytes, const FfnArgs& a, hipStream_t s) {
-    if (blocks > INT32_MAX) return hipErrorInvalidConfiguration;
-    if (lds_bytes > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds_bytes, s, a);
-    return hipGetLastError();
-}
-
-template <int T>
-hipError_t launch_tiles(const FfnArgs& a, int kernel, hipStream_t s) {
-    if (kernel == PO2Q_FFN_HIDDEN_SPLIT)
-        return launch(ffn_split_kernel<T>, ((int64_t)a.M + 15) / 16, (size_t)4 * T * 64 * sizeof(f32x4), a, s);
-    constexpr int TW = tiles_per_wave(T);
-    return launch(ffn_tiles_kernel<T, TW>, ((int64_t)a.M + 64 * TW - 1) / (64 * TW),
-                  2 * lds_buf_floats(T) * sizeof(float), a, s);
-}
-
-template <int... I>
-hipError_t launch_dim_tiles(int T, const FfnArgs& a, int kernel, hipStream_t s, std::integer_sequence<int, I...>) {
-    using Fn = hipError_t (*)(const FfnArgs&, int, hipStream_t);
-    static constexpr Fn table[] = {&launch_tiles<I + 1>...};
-    return table[T - 1](a, kernel, s);
 }
 
 }  // namespace
 
 hipError_t launch_ffn(const FfnArgs& a, int kernel, hipStream_t s) {
     if (kernel == PO2Q_FFN_AUTO) kernel = a.M <= kSplitMaxM ? PO2Q_FFN_HIDDEN_SPLIT : PO2Q_FFN_TOKEN_TILES;
-    return launch_dim_tiles((a.dim + 15) / 16, a, kernel, s, std::make_integer_sequence<int, kMaxT>());
+    return dispatch_tiles<kMaxT>((a.dim + 15) / 16, [&](auto tiles) {
+        constexpr int T = decltype(tiles)::value, TW = tiles_per_wave(T);
+        if (kernel == PO2Q_FFN_HIDDEN_SPLIT)
+            return launch_blocks(ffn_split_kernel<T>, ((int64_t)a.M + 15) / 16, 1, (size_t)4 * T * 64 * sizeof(f32x4),
+                                 s, a);
+        return launch_blocks(ffn_tiles_kernel<T, TW>, ((int64_t)a.M + 64 * TW - 1) / (64 * TW), 1,
+                             2 * lds_buf_floats(T) * sizeof(float), s, a);
+    });
 }
 
 }  // namespace po2q

@@ -13,8 +13,8 @@
 //     tile, no probability goes through LDS or a shuffle.
 //   * the denominator rides along.  Rows 8..15 of O^T are spare: row 8 of the V operand is 1.0, so O^T[8][query]
 //     accumulates sum_j p_j in the same MFMAs (and is rescaled with the rest).
-//   * the running max of a query must agree in the four lanes that share lane & 15: two lane exchanges (xor 16,
-//     xor 32) per group of up to four key tiles.
+//   * the running max of a query must agree in the four lanes that share lane & 15: one quad_max (po2q_vit_dev.h,
+//     two lane exchanges) per group of up to four key tiles.
 //   * scale * log2(e) is folded into Q once per wave; p = v_exp_f32(s - m).  Keys >= N are set to -inf before the
 //     max (p exactly 0, and every group holds a real key, so the max is finite); their K / V operands are zeros.
 //     N == 1 gives p = 1.0, denominator 1.0 and out == v bit for bit.
@@ -29,12 +29,11 @@
 #include <algorithm>
 
 #include "po2q_internal.h"
+#include "po2q_vit_dev.h"
 
 namespace po2q {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kHeads = 4, kDim = 8;
 constexpr int kRow = 3 * kHeads * kDim;  // floats per token row of qkv: [q | k | v]
@@ -71,9 +70,7 @@ __device__ __forceinline__ void key_group(Running& st, float q0, float q1, int k
             sc[u] = s;
         }
     }
-    cmax = fmaxf(cmax, __shfl_xor(cmax, 16));
-    cmax = fmaxf(cmax, __shfl_xor(cmax, 32));
-    const float m = fmaxf(st.m, cmax);
+    const float m = fmaxf(st.m, quad_max(cmax));
     const float alpha = __builtin_amdgcn_exp2f(st.m - m);  // first group: exp2(-inf) = 0 on O^T = 0
     st.m = m;
 #pragma unroll
@@ -193,20 +190,14 @@ __global__ __launch_bounds__(256) void mhsa_tiles_kernel(const float* __restrict
 bool mhsa_supported(int heads, int dim_head) { return heads == kHeads && dim_head == kDim; }
 
 hipError_t launch_mhsa(const float* qkv, float* out, int S, int N, float scale, hipStream_t s) {
-    const float qscale = scale * 1.44269504088896341f;  // p = 2^(qscale q.k - m)
-    if (N <= 16) {
-        hipLaunchKernelGGL(mhsa_heads_kernel, dim3(S), dim3(256), 0, s, qkv, out, N, qscale);
-        return hipGetLastError();
-    }
+    const float qscale = scale * kLog2e;  // p = 2^(qscale q.k - m)
+    if (N <= 16) return launch_blocks(mhsa_heads_kernel, S, 1, 0, s, qkv, out, N, qscale);
     const int ntiles = (N + 15) / 16;
     const int lds_keys = std::min(kLdsKeys, 16 * ntiles);
     const size_t lds_bytes = ((size_t)2 * lds_keys * kLdsRow + 4) * sizeof(float);  // + 4: see the kernel's V rows
     const int qblocks = (ntiles + 4 * kTilesPerWave - 1) / (4 * kTilesPerWave);
-    const int64_t blocks = (int64_t)S * kHeads * qblocks;
-    if (blocks > INT32_MAX) return hipErrorInvalidConfiguration;
-    hipLaunchKernelGGL(mhsa_tiles_kernel, dim3((unsigned)blocks), dim3(256), lds_bytes, s, qkv, out, N, qscale, lds_keys,
-                       qblocks);
-    return hipGetLastError();
+    return launch_blocks(mhsa_tiles_kernel, (int64_t)S * kHeads * qblocks, 1, lds_bytes, s, qkv, out, N, qscale,
+                         lds_keys, qblocks);
 }
 
 }  // namespace po2q

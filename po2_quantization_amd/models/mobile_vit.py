@@ -52,6 +52,15 @@ NATIVE_FFN = os.environ.get("PO2Q_NATIVE_FFN") == "1"
 NATIVE_PROJ = os.environ.get("PO2Q_NATIVE_PROJ") == "1"
 
 
+def _native_forward_ok(t, module, dropout_p):
+    """Whether `module` may run the forward-only native kernels on t: an fp32 HIP forward with no active dropout
+    and no gradient recorded, neither through t nor into a parameter of `module`."""
+    return (t.device.type == "cuda" and t.dtype == torch.float32
+            and not (module.training and dropout_p > 0)
+            and not (torch.is_grad_enabled() and (t.requires_grad or any(w.requires_grad
+                                                                         for w in module.parameters()))))
+
+
 def quantized_conv_1x1_bn(inp, oup, quantize_fn=None, bits=4):
     return nn.Sequential(QuantizedConv2d(inp, oup, 1, 1, 0, bias=False, quantize_fn=quantize_fn, bits=bits),
                          nn.BatchNorm2d(oup), nn.SiLU())
@@ -97,20 +106,16 @@ class Attention(nn.Module):
     def forward(self, x, add_input=False):
         """attention(x), or x + attention(x) with add_input (what Transformer.forward wants)."""
         b, p, n, _ = x.shape
-        proj = (NATIVE_PROJ and x.device.type == "cuda" and x.dtype == torch.float32
-                and not (self.training and self.dropout.p > 0)
-                and not (torch.is_grad_enabled() and (x.requires_grad or any(w.requires_grad
-                                                                             for w in self.parameters()))))
+        proj = NATIVE_PROJ and _native_forward_ok(x, self, self.dropout.p)
         if proj:
-            # fp32 HIP forward with no gradient recorded and no active dropout: LayerNorm + to_qkv as one launch
+            # LayerNorm + to_qkv as one launch
             # (1x1 patches hand in a strided view: the kernel reads rows, so the block's first layer copies once)
             x = x.contiguous()
             qkv = _lib.ln_linear(x, self.to_qkv.weight, self.norm.weight, self.norm.bias, self.norm.eps)
         else:
             qkv = self.to_qkv(self.norm(x))
-        if (NATIVE_ATTENTION and qkv.device.type == "cuda" and qkv.dtype == torch.float32 and not qkv.requires_grad
-                and not (self.training and self.dropout.p > 0)):
-            # fp32 HIP forward with no gradient recorded and no active dropout: one fused launch, no copies
+        if NATIVE_ATTENTION and _native_forward_ok(qkv, self, self.dropout.p):
+            # one fused launch, no copies
             out = _lib.mhsa(qkv, self.heads, self.scale)
         else:
             # [b, p, n, 3*h*d] -> q, k, v each [b, p, h, n, d]
@@ -134,9 +139,7 @@ class Transformer(nn.Module):
     def forward(self, x):
         for attn, ff in self.layers:
             x = attn(x, add_input=True)
-            if (NATIVE_FFN and x.device.type == "cuda" and x.dtype == torch.float32 and not x.requires_grad
-                    and not (ff.training and ff.net[3].p > 0)):
-                # fp32 HIP forward with no gradient recorded and no active dropout: one fused launch
+            if NATIVE_FFN and _native_forward_ok(x, ff, ff.net[3].p):  # one fused launch
                 norm, fc1, fc2 = ff.net[0], ff.net[1], ff.net[4]
                 # (1x1 patches make MobileViTBlock's rearrange a strided view and the add above keeps its layout:
                 # the kernel reads rows, so the first layer copies once; its output is contiguous for the others)

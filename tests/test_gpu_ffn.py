@@ -113,3 +113,40 @@ def test_model_logits_with_native_ffn(spec, monkeypatch):
         monkeypatch.setattr(mobile_vit, "NATIVE_ATTENTION", True)  # the two switches together
         e = normwise_err(m(x).cpu().numpy(), ref)
         assert e <= LOGIT_TOL and len(calls) == 36, (e, len(calls))
+
+
+def test_trainable_ffn_keeps_its_gradient(monkeypatch):
+    """Grad enabled, frozen attention, trainable FeedForward, an input that records no gradient: the MLP half has to
+    run the torch ops (the native kernels are forward only), though nothing upstream of it requires grad.
+
+    The frozen attention half is itself eligible for the native kernels, so with the switches on it runs them and the
+    output differs from the all-switches-off output by their rounding.  Bit for bit is therefore asserted against the
+    forward that differs in NATIVE_FFN alone (same attention path, the MLP half on torch ops in both), and the
+    all-switches-off forward has to agree within the parity contract."""
+    torch.manual_seed(3)
+    tr = mobile_vit.Transformer(24, 1, 4, 8, 48).to(DEV).train()
+    attn, ff = tr.layers[0]
+    for w in attn.parameters():
+        w.requires_grad_(False)
+    x = torch.randn(1, 2, 9, 24, device=DEV)
+    assert torch.is_grad_enabled() and not x.requires_grad
+    off = tr(x)
+    monkeypatch.setattr(mobile_vit, "NATIVE_ATTENTION", True)
+    monkeypatch.setattr(mobile_vit, "NATIVE_PROJ", True)
+    attn_only = tr(x)
+
+    def no_ffn(*a, **k):
+        raise AssertionError("the forward-only fused MLP ran under a recorded gradient")
+
+    monkeypatch.setattr(_lib, "ffn", no_ffn)
+    monkeypatch.setattr(mobile_vit, "NATIVE_FFN", True)
+    y = tr(x)
+    assert y.requires_grad
+    err = normwise_err(y.detach().cpu().numpy(), off.detach().cpu().numpy())
+    print("all switches on vs attention switches on: equal %s; vs all off: normwise %.3g" % (torch.equal(y, attn_only),
+                                                                                             err))
+    assert torch.equal(y, attn_only)
+    assert err <= CONV_TOL, err
+    y.sum().backward()
+    g = ff.net[1].weight.grad
+    assert g is not None and bool(g.abs().max() > 0)

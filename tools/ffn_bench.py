@@ -11,9 +11,7 @@ median over the runs and their min / max are reported, one JSON line per shape, 
 against an fp64 evaluation of the first 256 tokens.
 """
 import argparse
-import json
 import os
-import statistics
 import sys
 
 import torch
@@ -21,6 +19,7 @@ import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import _ab  # noqa: E402  (tools/_ab.py, next to this script)
 from po2_quantization_amd import _lib  # noqa: E402
 
 EPS = 1e-5
@@ -28,16 +27,6 @@ EPS = 1e-5
 
 def torch_ffn(x, ln_w, ln_b, w1, b1, w2, b2):
     return x + F.linear(F.silu(F.linear(F.layer_norm(x, x.shape[-1:], ln_w, ln_b, EPS), w1, b1)), w2, b2)
-
-
-def run_us(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) * 1e3 / iters
 
 
 def main():
@@ -50,7 +39,6 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     ops = _lib.ops()
-    lines = []
     for shape in args.shapes:
         M, dim, hidden = (int(v) for v in shape.split("x"))
         torch.manual_seed(M + dim)
@@ -62,25 +50,11 @@ def main():
         arms = {"torch": lambda: torch_ffn(x, *p)}
         for name, kernel in (("token_tiles", 1), ("hidden_split", 2), ("auto", 0)):
             arms[name] = lambda kernel=kernel: ops.ffn(x, ln_w, ln_b, EPS, w1, b1, w2, b2, True, kernel)
-        with torch.no_grad():
-            ref = torch_ffn(x[:64].double().cpu(), *(t.double().cpu() for t in p))
-            res = {"kind": "ffn_ab", "M": M, "dim": dim, "hidden": hidden, "iters": args.iters, "runs": args.runs}
-            for name, fn in arms.items():
-                res[name + "_vs_fp64_normwise"] = float((fn()[:64].cpu().double() - ref).abs().max() / ref.abs().max())
-                run_us(fn, args.iters)  # warm-up
-            times = {name: [] for name in arms}
-            for _ in range(args.runs):
-                for name, fn in arms.items():
-                    times[name].append(run_us(fn, args.iters))
-        for name, v in times.items():
-            res[name + "_us"] = round(statistics.median(v), 2)
-            res[name + "_us_min_max"] = [round(min(v), 2), round(max(v), 2)]
+        res = {"kind": "ffn_ab", "M": M, "dim": dim, "hidden": hidden, "iters": args.iters, "runs": args.runs}
+        res.update(_ab.ab(arms, lambda: torch_ffn(x[:64].double().cpu(), *(t.double().cpu() for t in p)),
+                          lambda y: y[:64], args.iters, args.runs))
         res["speedup_auto"] = round(res["torch_us"] / res["auto_us"], 2)
-        lines.append(json.dumps(res))
-        print(lines[-1], flush=True)
-    if args.out:
-        with open(args.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+        _ab.emit(res, args.out)
 
 
 if __name__ == "__main__":

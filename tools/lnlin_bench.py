@@ -12,9 +12,7 @@ per arm the median over the runs and their min / max are reported, one JSON line
 difference against an fp64 evaluation of the first 256 tokens.
 """
 import argparse
-import json
 import os
-import statistics
 import sys
 
 import torch
@@ -22,6 +20,7 @@ import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import _ab  # noqa: E402  (tools/_ab.py, next to this script)
 from po2_quantization_amd import _lib  # noqa: E402
 
 EPS = 1e-5
@@ -37,16 +36,6 @@ def torch_out(x, w, bias, residual):
     return residual + F.linear(x, w, bias)
 
 
-def run_us(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) * 1e3 / iters
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="+", default=DEFAULT, help="half:M x in_dim x out_dim, half in {qkv, out}")
@@ -56,7 +45,6 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     ops = _lib.ops()
-    lines = []
     for shape in args.shapes:
         half, _, dims = shape.partition(":")
         M, in_dim, out_dim = (int(v) for v in dims.split("x"))
@@ -76,27 +64,11 @@ def main():
                                     residual[:64].double().cpu())
         for name, kernel in (("resident", 1), ("out_split", 2), ("auto", 0)):
             arms[name] = lambda kernel=kernel: native(kernel)
-        with torch.no_grad():
-            want = ref()
-            res = {"kind": "lnlin_ab", "half": half, "M": M, "in_dim": in_dim, "out_dim": out_dim, "iters": args.iters,
-                   "runs": args.runs}
-            for name, fn in arms.items():
-                got = fn()[:64].cpu().double()
-                res[name + "_vs_fp64_normwise"] = float((got - want).abs().max() / want.abs().max())
-                run_us(fn, args.iters)  # warm-up
-            times = {name: [] for name in arms}
-            for _ in range(args.runs):
-                for name, fn in arms.items():
-                    times[name].append(run_us(fn, args.iters))
-        for name, v in times.items():
-            res[name + "_us"] = round(statistics.median(v), 2)
-            res[name + "_us_min_max"] = [round(min(v), 2), round(max(v), 2)]
+        res = {"kind": "lnlin_ab", "half": half, "M": M, "in_dim": in_dim, "out_dim": out_dim, "iters": args.iters,
+               "runs": args.runs}
+        res.update(_ab.ab(arms, ref, lambda y: y[:64], args.iters, args.runs))
         res["speedup_auto"] = round(res["torch_us"] / res["auto_us"], 2)
-        lines.append(json.dumps(res))
-        print(lines[-1], flush=True)
-    if args.out:
-        with open(args.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+        _ab.emit(res, args.out)
 
 
 if __name__ == "__main__":

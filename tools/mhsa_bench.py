@@ -10,15 +10,14 @@ with device events; per arm the median over the runs and their min / max are rep
 with the two arms' normwise difference against an fp64 evaluation of 8 of the sequences.
 """
 import argparse
-import json
 import os
-import statistics
 import sys
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import _ab  # noqa: E402  (tools/_ab.py, next to this script)
 from po2_quantization_amd import _lib  # noqa: E402
 
 HEADS, DIM_HEAD = 4, 8
@@ -32,16 +31,6 @@ def torch_core(qkv):
     return torch.matmul(attn, v).transpose(2, 3).reshape(b, p, n, -1)
 
 
-def run_us(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) * 1e3 / iters
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seqs", type=int, default=256)
@@ -52,31 +41,15 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     ops = _lib.ops()
-    lines = []
     for n in args.tokens:
         torch.manual_seed(n)
         qkv = torch.randn(args.seqs // 4, 4, n, 3 * HEADS * DIM_HEAD, device=dev)
         arms = {"torch": lambda: torch_core(qkv), "native": lambda: ops.mhsa(qkv, HEADS, SCALE)}
-        with torch.no_grad():
-            ref = torch_core(qkv[:2].double().cpu())
-            res = {"kind": "mhsa_ab", "seqs": args.seqs, "tokens": n, "heads": HEADS, "dim_head": DIM_HEAD,
-                   "iters": args.iters, "runs": args.runs}
-            for name, fn in arms.items():
-                res[name + "_vs_fp64_normwise"] = float((fn()[:2].cpu().double() - ref).abs().max() / ref.abs().max())
-                run_us(fn, args.iters)  # warm-up
-            times = {name: [] for name in arms}
-            for _ in range(args.runs):
-                for name, fn in arms.items():
-                    times[name].append(run_us(fn, args.iters))
-        for name, v in times.items():
-            res[name + "_us"] = round(statistics.median(v), 2)
-            res[name + "_us_min_max"] = [round(min(v), 2), round(max(v), 2)]
+        res = {"kind": "mhsa_ab", "seqs": args.seqs, "tokens": n, "heads": HEADS, "dim_head": DIM_HEAD,
+               "iters": args.iters, "runs": args.runs}
+        res.update(_ab.ab(arms, lambda: torch_core(qkv[:2].double().cpu()), lambda y: y[:2], args.iters, args.runs))
         res["speedup"] = round(res["torch_us"] / res["native_us"], 2)
-        lines.append(json.dumps(res))
-        print(lines[-1], flush=True)
-    if args.out:
-        with open(args.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+        _ab.emit(res, args.out)
 
 
 if __name__ == "__main__":
